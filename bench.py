@@ -25,6 +25,10 @@ Three tiers, never mixed:
                      compared with the kernel tier's results (whole_node.parity) -- the two tiers measure the same job
   cpu_baseline       the C oracle on one host core, bounded sample
 
+A plain run sets up, warms up, times --steps steps and prints the line (value, ms_per_step, roofline from the run's own
+hipEvents); whole_node / end_to_end and cpu_baseline take minutes of their own and are measured only with --full (they
+are null otherwise).  --dump-outputs DIR writes the result vectors of the last timed step as DIR/<name>.npy (float64).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -248,17 +252,59 @@ def k1_floor_model(k1_ms):
         return {"error": repr(ex)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, res, order_dep=None):
+    """--dump-outputs: what a caller of the timed path receives from its last step (rsqc_results), one float64 .npy per
+    vector: counters in abi.COUNTER_NAMES order, every per-gene / per-exon / fragment / GC vector the run filled (empty ones
+    are not written) and the scalars as 1-element arrays.  On the reduce path the order-dependent outputs are those composed
+    across the ranks (merge_order_dependent).  Every value is an integer below 2^53 or a float64, so the cast is exact;
+    the workload's vectors come to ~15 MB.  Every value written is finite.  Two runs agree bit for bit except exon_reads,
+    sums of float64 atomics whose last bits follow the order the atomics land in (~1e-14 relative)."""
+    from rnaseqc_amd import abi
+    arrays = {"counters": res.counters}
+    for name in abi.Results._VEC:
+        arrays[name] = getattr(res, name)
+    scalars = {"read_length": res.read_length, "fragment_samples_remaining": res.fragment_samples_remaining,
+               "gc_out_of_range": res.gc_out_of_range, "exons_outside_gene_row": res.exons_outside_gene_row}
+    if order_dep:
+        scalars["read_length"], arrays["fragment_size"], arrays["fragment_count"], scalars["fragment_samples_remaining"] = order_dep[:4]
+    arrays.update({k: np.array([v]) for k, v in scalars.items()})
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items() if np.asarray(v).size}
+    # gene_cov_cv is std / mean as the reference computes it (src/Metrics.cpp:332): 0 / 0 = NaN for a gene whose masked
+    # coverage is all zero (its mean and std are 0; the metrics file's CV median leaves it out).  Those entries are written
+    # as 0, like the genes without statistics; any other non-finite value is an error of the run, not dumped.
+    if "gene_cov_cv" in arrays:
+        cv = arrays["gene_cov_cv"]
+        arrays["gene_cov_cv"] = np.where(np.isnan(cv) & (arrays["gene_cov_mean"] == 0) & (arrays["gene_cov_std"] == 0), 0.0, cv)
+    bad = sorted(k for k, v in arrays.items() if not np.isfinite(v).all())
+    if bad:
+        raise SystemExit("--dump-outputs: non-finite values in %s" % ", ".join(bad))
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of results, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return {"dir": dirname, "files": len(arrays), "bytes": total}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--pairs", type=int, default=50_000_000, help="read pairs of the whole job (2 records each + 1.5 %% copies + 1 %% unmapped)")
-    ap.add_argument("--cpu-sample", type=int, default=60_000_000, help="records timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: cpu_baseline "
+                                                        "(--cpu-sample) and the whole_node / end_to_end tier (unless --no-e2e)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the result vectors of the last step as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-sample", type=int, default=60_000_000, help="records timed on the CPU oracle with --full (0 = skip)")
     ap.add_argument("--workers", type=int, default=0, help="generator processes (0 = min(usable CPUs, 24))")
     ap.add_argument("--chr1", action="store_true", help="(diagnostic) BASELINE.json configs[1]: chr1-like GTF + --pairs pairs "
                                                          "(default 5 M) on one GPU; output marked invalid")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end_to_end tier (CLI on a BAM of the same records)")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end_to_end tier (CLI on a BAM of the same records)")
     ap.add_argument("--e2e-real", type=int, default=50_000_000, help="records of the realistic-entropy BAM flavour (0 = skip)")
     ap.add_argument("--e2e-threads", type=int, default=0, help="RSQC_HOST_THREADS for the CLI runs (0 = its default)")
     ap.add_argument("--tmp", default="", help="directory for the end_to_end files (default: the system temp dir)")
@@ -274,6 +320,10 @@ def main():
     ap.add_argument("--legacy", action="store_true", help="(diagnostic) the --legacy counting rules; output marked invalid")
     ap.add_argument("--bed", action="store_true", help="BASELINE configs[4] on the GPUs given: the same workload with BED intervals, i.e. the fragment-size sampler on (per-base coverage and the bias windows are always computed)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.no_finalize:
+        ap.error("--dump-outputs needs the results of a step: not with --no-finalize")
 
     # RCCL prints a version banner on stdout when the communicator comes up; the contract is ONE JSON line there,
     # so everything else this process (and the libraries it loads) writes to fd 1 is sent to stderr.
@@ -317,7 +367,7 @@ def main():
     elif world > 1 or args.dist_selftest:
         # sharded runs submit one batch per owned contig: a batch is a contiguous range of the file, and the
         # order-dependent outputs are composed per batch in file order (rsqc_shard_info)
-        want_e2e = rank == 0 and not args.no_e2e and not (args.no_finalize or args.host_fed or args.fasta or args.legacy or args.bed)
+        want_e2e = args.full and rank == 0 and not args.no_e2e and not (args.no_finalize or args.host_fed or args.fasta or args.legacy or args.bed)
         if want_e2e and world > 1:
             # rank 0 also runs the whole-node tier (`rnaseqc --gpus N` on a BAM of ALL the records): it generates every contig
             # and keeps its own for the kernel tier
@@ -451,6 +501,10 @@ def main():
     total_records = sum(per_rank)
     tm = e.timing()
 
+    if rank == 0 and args.dump_outputs:
+        d = dump_outputs(args.dump_outputs, res, order_dep[0])
+        log("outputs of the last step: %d arrays, %.1f MB in %s" % (d["files"], d["bytes"] / 1e6, d["dir"]))
+
     if rank == 0:
         k1_ms = tm["classify_ms"] / max(tm["classify_launches"], 1)
         k1_long_ms = tm.get("classify_long_ms", 0.0) / max(tm["classify_launches"], 1)       # classify_long_kernel: the ~1 % of the records K1 defers
@@ -470,7 +524,7 @@ def main():
                 else:
                     traffic_note = "profiles/k1_traffic.json was measured on other K1 code (hash %s, now %s): dropped" % (tj.get("k1_code_hash"), k1_code_hash())
         cpu = None
-        if args.cpu_sample > 0 and world == 1 and batch is not None:          # the CPU baseline is a single-GPU-run item (rank 0, N = 1)
+        if args.full and args.cpu_sample > 0 and world == 1 and batch is not None:   # the CPU baseline is a single-GPU-run item (rank 0, N = 1)
             from oracle import binding
             ns = min(args.cpu_sample, batch.n)
             sample = batch.slice(0, ns) if ns < batch.n else batch
@@ -486,7 +540,7 @@ def main():
                              "SoA input, no BAM decode, incl. its end-of-file stage" % ns, "seconds": round(tc, 3)}
             del sample
         e2e = None
-        if not args.no_e2e and not (args.no_finalize or args.host_fed or args.fasta or args.legacy or args.bed):
+        if args.full and not args.no_e2e and not (args.no_finalize or args.host_fed or args.fasta or args.legacy or args.bed):
             try:
                 rl_now = int(order_dep[0][0]) if order_dep[0] else int(res.read_length)
                 if reduce_path:

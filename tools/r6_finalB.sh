@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 OUT=gpurun_out/r6finalB; mkdir -p $OUT
 T0=$(date +%s)
 timeout 900 python -m pytest tests -m gpu -x -q > $OUT/tests.log 2>&1; echo "tests rc $? ($(( $(date +%s) - T0 )) s)"; grep -E "passed|failed" $OUT/tests.log | tail -1
-timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc $? ($(( $(date +%s) - T0 )) s)"
+timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc $? ($(( $(date +%s) - T0 )) s)"
 python -c "
 import json; d=json.loads(open('$OUT/bench_default.json').read().strip().splitlines()[-1])
 print('step', d['ms_per_step'], 'value', d['value'], 'frac', d['roofline']['frac'], 'traffic', d['roofline']['traffic'], d['roofline'].get('traffic_note'), d['stage_ms'])
