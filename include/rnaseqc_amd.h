@@ -578,6 +578,20 @@ RSQC_API int rsqc_decode_submit(rsqc_ctx *ctx, const void *compressed, uint64_t 
 /* End of the stream: RSQC_ERR_INPUT if an incomplete record is left over ("truncated BAM record").             */
 RSQC_API int rsqc_decode_end(rsqc_ctx *ctx, rsqc_decode_info *out);
 
+/* ---- device-side SAM text decode ------------------------------------------------------------------------------
+ * The same stream for SAM input (the reference opens SAM, BGZF-compressed SAM and BAM alike through htslib, src/BamReader.h):
+ * plain text through rsqc_decode_submit_text, BGZF-compressed SAM through rsqc_decode_submit (blocks as for BAM; skip_bytes
+ * may cover the header text).  ref_names: the header's @SQ SN values in order, p->n_ref of them (copied).  Lines starting with
+ * '@' in front of the stream's first alignment are header lines and are skipped; any other malformed line (fewer than 11
+ * fields, a number that does not parse or overflows its column, an unknown CIGAR operator, SEQ / CIGAR or SEQ / QUAL
+ * lengths that differ, a '@' line after the first alignment) is RSQC_ERR_INPUT, and rsqc_last_error names its 1-based line
+ * number, counted from the first byte of the stream.  An RNAME the names do not hold, and POS 0 on a named reference, give
+ * RefID -1 and the unmapped flag bit.  The bytes after a call's last '\n' are carried to the next call on the device; a last
+ * line without '\n' is ended by rsqc_decode_end.  rsqc_decode_end / rsqc_decode_info as for BAM (bad_refid: the names
+ * of judged records with RefID -1).                                                                                         */
+RSQC_API int rsqc_decode_begin_sam(rsqc_ctx *ctx, const rsqc_decode_params *p, const char *const *ref_names);
+RSQC_API int rsqc_decode_submit_text(rsqc_ctx *ctx, const void *text, uint64_t bytes, rsqc_decode_window *out);
+
 RSQC_API const char *rsqc_strerror(int code);
 RSQC_API const char *rsqc_last_error(rsqc_ctx *ctx);
 RSQC_API const char *rsqc_counter_name(int counter);   /* the reference's Metrics key  */

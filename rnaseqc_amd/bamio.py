@@ -75,6 +75,96 @@ def write_bam(path, contigs, batch, qnames=None, filter_tag="XF", ch_tag="ch", l
         f.write(_EOF)
 
 
+def sam_consistent(batch):
+    """The batch with SEQ lengths a SAM file can hold: a record with operations gets l_qseq = its CIGAR's query length
+    (M / I / S / = / X), which SAM requires and BAM does not (synthetic batches draw the two independently).  Write the
+    BAM, the SAM and the expected results from the SAME adjusted batch."""
+    import dataclasses
+    lq = batch.l_qseq.astype(np.int64)
+    nm = batch.nm.astype(np.int64)
+    nc = batch.n_cigar.astype(np.int64)
+    widx = batch.wide_index.astype(np.int64)
+    lq[widx] = batch.wide_l_qseq; nm[widx] = batch.wide_nm; nc[widx] = batch.wide_n_cigar
+    ops = batch.cigar.astype(np.int64)
+    q = np.where(np.isin(ops & 15, (0, 1, 4, 7, 8)), ops >> 4, 0)
+    cs = np.concatenate([[0], np.cumsum(q)])
+    off = batch.cigar_off.astype(np.int64)
+    lq = np.where(nc > 0, cs[off + nc] - cs[off], lq)
+    wide = (lq >= abi.LQSEQ_ESCAPE) | (nm >= abi.NM_ESCAPE) | (nm < 0) | (nc >= abi.NCIGAR_ESCAPE)
+    wi = np.flatnonzero(wide)
+    return dataclasses.replace(batch, l_qseq=np.where(lq >= abi.LQSEQ_ESCAPE, abi.LQSEQ_ESCAPE, lq).astype(batch.l_qseq.dtype),
+                               wide_index=wi.astype(np.uint64), wide_nm=nm[wi].astype(np.int32), wide_l_qseq=lq[wi].astype(np.int32),
+                               wide_n_cigar=nc[wi].astype(np.uint32))
+
+
+_CIGAR_CH = "MIDNSHP=X"
+
+
+def write_sam(path, contigs, batch, qnames=None, ch_tag="ch", filter_tag="XF", bgzf=False, extra_aux=None, level=1):
+    """The records of write_bam (same names, flags, mates, tags) as SAM text; bgzf=True: BGZF-compressed SAM.
+    SEQ is all 'A' (or '*' when empty), QUAL '*'.  CIGAR query lengths must equal l_qseq (sam_consistent).
+    extra_aux: optional callable i -> (text before, text after) of further optional fields ("TG:T:value" joined by tabs)."""
+    n = batch.n
+    tid = batch.tid_per_record()
+    names = [c[0] for c in contigs]
+    wide = {int(i): k for k, i in enumerate(batch.wide_index)}
+    lines = ["@HD\tVN:1.6\tSO:coordinate"] + ["@SQ\tSN:%s\tLN:%d" % (nm, ln) for nm, ln in contigs]
+    for i in range(n):
+        name = qnames[i] if qnames is not None else bytes(batch.qname[int(batch.qname_off[i]):int(batch.qname_off[i + 1])])
+        if isinstance(name, bytes):
+            name = name.decode("latin-1")
+        lq, nm, nc = int(batch.l_qseq[i]), int(batch.nm[i]), int(batch.n_cigar[i])
+        if i in wide:
+            k = wide[i]
+            lq, nm, nc = int(batch.wide_l_qseq[k]), int(batch.wide_nm[k]), int(batch.wide_n_cigar[k])
+        cig = batch.cigar[int(batch.cigar_off[i]):int(batch.cigar_off[i]) + nc]
+        cigar = "".join("%d%s" % (int(o) >> 4, _CIGAR_CH[int(o) & 15]) for o in cig) if nc else "*"
+        tb = int(batch.tagbits[i])
+        t = int(tid[i])
+        mtid = t if (tb & abi.TB_MTID_SAME) else (t + 1 if t + 1 < len(contigs) else (0 if t != 0 else -1))
+        rname = names[t] if t >= 0 else "*"
+        rnext = "=" if (mtid == t and t >= 0) else ("*" if mtid < 0 else names[mtid])
+        tags = []
+        if tb & abi.TB_HAS_NM:
+            tags.append("NM:i:%d" % nm)
+        if tb & abi.TB_HAS_CH:
+            tags.append("%s:Z:1" % ch_tag)
+        if tb & abi.TB_FILTER0:
+            tags.append("%s:i:1" % filter_tag)
+        if extra_aux is not None:
+            before, after = extra_aux(i)
+            tags = ([before] if before else []) + tags + ([after] if after else [])
+        fields = [name, str(int(batch.flag[i])), rname, str(int(batch.pos[i]) + 1), str(int(batch.mapq[i])), cigar, rnext,
+                  str(int(batch.mpos[i]) + 1), str(int(batch.isize[i])), "A" * lq if lq else "*", "*"] + tags
+        lines.append("\t".join(fields))
+    text = ("\n".join(lines) + "\n").encode("latin-1")
+    with open(path, "wb") as f:
+        if bgzf:
+            for o in range(0, len(text), 65280):
+                f.write(_bgzf_block(text[o:o + 65280], level))
+            f.write(_EOF)
+        else:
+            f.write(text)
+
+
+def write_sam_fast(path, contigs, batch, ch_tag="ch", filter_tag="XF", threads=16, seq_mode=0, bgzf=False, struct=None):
+    """Same records as write_sam (and as write_bam_fast: records without names get 16 hex digits of their qhash) through the C++
+    host library's threaded writer (host_sam_write), for multi-million-record runs.  seq_mode 1: random bases and binned
+    qualities (the BAM writer's seq_mode 1).  CIGAR query lengths must equal l_qseq (sam_consistent)."""
+    import ctypes as C
+    import os
+    lib = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "librsqc_host.so"))
+    names = (C.c_char_p * len(contigs))(*[c[0].encode() for c in contigs])
+    lens = (C.c_uint * len(contigs))(*[int(c[1]) for c in contigs])
+    st = struct if struct is not None else batch.to_struct()
+    lib.host_sam_write.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_uint), C.c_int, C.c_void_p, C.c_char_p, C.c_char_p,
+                                   C.c_int, C.c_int, C.c_int]
+    rc = lib.host_sam_write(str(path).encode(), names, lens, len(contigs), C.byref(st), ch_tag.encode(), filter_tag.encode(),
+                            threads, seq_mode, 1 if bgzf else 0)
+    if rc:
+        raise OSError("host_sam_write failed: %d" % rc)
+
+
 def write_gtf(path, ann):
     with open(path, "w") as f:
         f.write("##synthetic collapsed annotation\n")

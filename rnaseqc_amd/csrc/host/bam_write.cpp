@@ -216,3 +216,95 @@ HAPI int host_bam_write(const char *path, const char *const *contig_names, const
                         const rsqc_batch *b, const char *ch_tag, const char *filter_tag, int threads) {
     return host_bam_write_ex(path, contig_names, contig_len, n_contigs, b, ch_tag, filter_tag, threads, 0, 0, nullptr);
 }
+
+// The same records as host_bam_write_ex (names, flags, mates, tags; records without names get 16 hex digits of their qhash)
+// as SAM text, plain or BGZF-compressed (bgzf != 0), by the same pool of threads.  SEQ and QUAL: seq_mode 0 all 'A' / '*';
+// seq_mode 1 the random bases and binned qualities of the BAM writer's seq_mode 1.  CIGAR query lengths must equal l_qseq
+// (bamio.sam_consistent).  Returns 0, or 10 when the file cannot be written.
+HAPI int host_sam_write(const char *path, const char *const *contig_names, const unsigned *contig_len, int n_contigs,
+                        const rsqc_batch *b, const char *ch_tag, const char *filter_tag, int threads, int seq_mode, int bgzf) {
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return 10;
+    if (threads < 1) threads = 1;
+    WorkPool pool(threads);
+    auto put = [&](const std::vector<uint8_t> &raw) -> bool {
+        if (!bgzf) return fwrite(raw.data(), 1, raw.size(), fp) == raw.size();
+        std::vector<uint8_t> comp; std::vector<uint64_t> bo;
+        deflate_blocks(raw.data(), raw.size(), comp, bo);
+        return fwrite(comp.data(), 1, comp.size(), fp) == comp.size();
+    };
+    {
+        std::string text = "@HD\tVN:1.6\tSO:coordinate\n";
+        for (int i = 0; i < n_contigs; ++i) text += std::string("@SQ\tSN:") + contig_names[i] + "\tLN:" + std::to_string(contig_len[i]) + "\n";
+        if (!put(std::vector<uint8_t>(text.begin(), text.end()))) { fclose(fp); return 10; }
+    }
+    static const char kOp[] = "MIDNSHP=X???????";
+    const uint64_t GROUP = 1u << 15;
+    const uint64_t n_groups = (b->n + GROUP - 1) / GROUP;
+    const size_t wave = (size_t)threads * 2;
+    std::vector<std::vector<uint8_t>> out(wave);
+    for (uint64_t g0 = 0; g0 < n_groups; g0 += wave) {
+        const size_t ng = (size_t)std::min<uint64_t>(wave, n_groups - g0);
+        pool.run(ng, [&](size_t k) {
+            std::string t;
+            const uint64_t r0 = (g0 + k) * GROUP, r1 = std::min<uint64_t>(r0 + GROUP, b->n);
+            t.reserve((size_t)(r1 - r0) * 400);
+            uint32_t seg = 0;
+            { uint32_t lo = 0, hi = b->n_seg; while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (b->seg_start[m] <= r0) lo = m; else hi = m; } seg = lo; }
+            uint32_t w = 0;
+            { uint32_t lo = 0, hi = b->n_wide; while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (b->wide_index[m] < r0) lo = m + 1; else hi = m; } w = lo; }
+            char num[64];
+            for (uint64_t i = r0; i < r1; ++i) {
+                while (seg + 1 < b->n_seg && b->seg_start[seg + 1] <= i) ++seg;
+                const int32_t tid = b->n_seg ? b->seg_tid[seg] : -1;
+                const rsqc_rec_core &co = b->core[i]; const rsqc_rec_aux &au = b->aux[i];
+                int32_t lq = au.l_qseq, nm = au.nm; uint32_t nc = au.n_cigar;
+                if (au.l_qseq == RSQC_LQSEQ_ESCAPE || au.nm == RSQC_NM_ESCAPE || au.n_cigar == RSQC_NCIGAR_ESCAPE) {
+                    while (w < b->n_wide && b->wide_index[w] < i) ++w;
+                    if (w < b->n_wide && b->wide_index[w] == i) { lq = b->wide_l_qseq[w]; nm = b->wide_nm[w]; nc = b->wide_n_cigar[w]; }
+                }
+                if (b->qname) t.append(b->qname + b->qname_off[i], b->qname_off[i + 1] - b->qname_off[i]);
+                else { snprintf(num, sizeof num, "%016llx", (unsigned long long)au.qhash); t += num; }
+                const int32_t mtid = (au.tagbits & RSQC_TB_MTID_SAME) ? tid : (tid + 1 < n_contigs ? tid + 1 : (tid != 0 ? 0 : -1));
+                snprintf(num, sizeof num, "\t%u\t", (unsigned)au.flag); t += num;
+                t += tid >= 0 && tid < n_contigs ? contig_names[tid] : "*";
+                snprintf(num, sizeof num, "\t%lld\t%u\t", (long long)co.pos + 1, (unsigned)au.mapq); t += num;
+                if (!nc) t += '*';
+                for (uint32_t o = 0; o < nc; ++o) { const uint32_t op = b->cigar[co.cigar_off + o]; snprintf(num, sizeof num, "%u%c", op >> 4, kOp[op & 15]); t += num; }
+                t += '\t';
+                t += (mtid == tid && tid >= 0) ? "=" : (mtid >= 0 && mtid < n_contigs ? contig_names[mtid] : "*");
+                snprintf(num, sizeof num, "\t%lld\t%d\t", (long long)co.mpos + 1, co.isize); t += num;
+                const size_t l_seq = lq < 0 ? 0 : (size_t)lq;
+                if (!l_seq) t += "*\t*";
+                else if (seq_mode == 0) { t.append(l_seq, 'A'); t += "\t*"; }
+                else {
+                    uint64_t s = au.qhash ^ ((uint64_t)au.flag << 48) ^ 0x9E3779B97F4A7C15ull; if (!s) s = 1;
+                    static const char base4[4] = {'A', 'C', 'G', 'T'};
+                    for (size_t j = 0; j < l_seq; j += 32) { uint64_t r = xs(s); for (size_t q = j; q < std::min(j + 32, l_seq); ++q, r >>= 2) t += base4[r & 3]; }
+                    t += '\t';
+                    static const uint8_t qbin[8] = {37, 37, 37, 37, 37, 25, 11, 2};
+                    uint8_t q = 37; uint64_t r = xs(s); int left = 0;
+                    for (size_t j = 0; j < l_seq; ++j) {
+                        if (left == 0) { r = xs(s); left = 12; }
+                        if ((r & 31) < 3) q = qbin[(r >> 5) & 7];
+                        r >>= 5; --left;
+                        t += (char)(q + 33);
+                    }
+                }
+                if (au.tagbits & RSQC_TB_HAS_NM) { snprintf(num, sizeof num, "\tNM:i:%d", nm); t += num; }
+                if (au.tagbits & RSQC_TB_HAS_CH) { t += '\t'; t += ch_tag[0]; t += ch_tag[1]; t += ":Z:1"; }
+                if (au.tagbits & RSQC_TB_FILTER0) { t += '\t'; t += filter_tag[0]; t += filter_tag[1]; t += ":i:1"; }
+                t += '\n';
+            }
+            out[k].assign(t.begin(), t.end());
+            if (bgzf) { std::vector<uint8_t> comp; std::vector<uint64_t> bo; deflate_blocks(out[k].data(), out[k].size(), comp, bo); out[k].swap(comp); }
+        });
+        for (size_t k = 0; k < ng; ++k)
+            if (fwrite(out[k].data(), 1, out[k].size(), fp) != out[k].size()) { fclose(fp); return 10; }
+    }
+    if (bgzf) {
+        static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        fwrite(eof, 1, 28, fp);
+    }
+    return fclose(fp) == 0 ? 0 : 10;
+}

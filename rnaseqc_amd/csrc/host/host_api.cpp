@@ -12,6 +12,7 @@
 #include "bgzf_feed.hpp"
 #include "gtf.hpp"
 #include "report.hpp"
+#include "sam_feed.hpp"
 
 using namespace rsqc_host;
 #define HAPI extern "C" __attribute__((visibility("default")))
@@ -167,3 +168,17 @@ HAPI int host_feed_next(void *hv, const uint8_t **data, unsigned long long *byte
 }
 HAPI const char *host_feed_error(void *hv) { return ((FeedHandle *)hv)->error.c_str(); }
 HAPI void host_feed_free(void *hv) { delete (FeedHandle *)hv; }
+
+// the input's format by content (host/sam_feed.cpp: 1 SAM text, 2 BGZF SAM, 3 BAM, -2 plain gzip, -1 unopenable, 0 unknown)
+// and, for SAM, its @SQ lines as "name:length,..." in out
+HAPI int host_sam_header(const char *path, char *out, int cap) {
+    const InputFormat f = sniff_file(path);
+    if (cap > 0) out[0] = 0;
+    if (f != InputFormat::SamText && f != InputFormat::SamBgzf) return (int)f;
+    SamHeader h;
+    if (!read_sam_header(path, h)) return -1;
+    std::string s;
+    for (size_t k = 0; k < h.names.size(); ++k) s += (k ? "," : "") + h.names[k] + ":" + std::to_string(h.lengths[k]);
+    if (cap > 0) { strncpy(out, s.c_str(), (size_t)cap - 1); out[cap - 1] = 0; }
+    return (int)f;
+}

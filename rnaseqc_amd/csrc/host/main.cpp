@@ -3,7 +3,9 @@
 // Host side only: GTF/BED ingest, BAM decode into SoA batches, report writers.  Every per-record
 // computation happens on the GPU through the C ABI (include/rnaseqc_amd.h); without a GPU the
 // program exits with code 10.
+#include <signal.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include <memory>
 #include <sys/types.h>
@@ -25,6 +27,7 @@
 #include "fasta.hpp"
 #include "gtf.hpp"
 #include "report.hpp"
+#include "sam_feed.hpp"
 
 using namespace rsqc_host;
 
@@ -223,8 +226,10 @@ uint64_t decode_reserve_bytes(uint64_t file_size) {
 }
 // One stream of BGZF blocks [voff_beg, voff_end) through the GPU: the feeder reads and frames the blocks, every chunk is one
 // rsqc_decode_submit.  on_window sees what each call decoded.  Returns an RSQC_* code; info describes the whole stream.
+// sam_names: the @SQ names of a BGZF-compressed SAM (the stream goes through the device SAM stages, rsqc_decode_begin_sam)
 template <class F>
-int decode_range(rsqc_ctx *gpu, BgzfFeeder &feed, const rsqc_decode_params &dp, uint64_t voff_beg, uint64_t voff_end, rsqc_decode_info &info, F &&on_window) {
+int decode_range(rsqc_ctx *gpu, BgzfFeeder &feed, const rsqc_decode_params &dp, uint64_t voff_beg, uint64_t voff_end, rsqc_decode_info &info, F &&on_window,
+                 const char *const *sam_names = nullptr) {
     // Calls are large on purpose: the inflate kernel runs one wave per BGZF block, twenty waves per CU = 5 120 on the chip, and a
     // call's time is that of its LAST block: a call of 5 300 blocks (128 MB of a file compressed 3 x, round 4's chunk) runs 180 of
     // them on an empty chip.  Up to 1 GB of inflated data = 16 000 blocks per call whatever the file's compression (the feeder reads
@@ -236,7 +241,7 @@ int decode_range(rsqc_ctx *gpu, BgzfFeeder &feed, const rsqc_decode_params &dp, 
     rsqc_decode_params dpr = dp;
     dpr.pipelined = 1;                          // a call's records are reported by the call after it (the last by rsqc_decode_end)
     dpr.reserve_inflated_bytes = decode_reserve_bytes(feed.file_size());
-    int rc = rsqc_decode_begin(gpu, &dpr);
+    int rc = sam_names ? rsqc_decode_begin_sam(gpu, &dpr, sam_names) : rsqc_decode_begin(gpu, &dpr);
     if (rc != RSQC_OK) return rc;
     const bool prof = getenv("RSQC_DECODE_PROFILE") != nullptr;
     double t_feed = 0;
@@ -398,6 +403,8 @@ int main(int argc, char **argv) {
         // later, where the reference reports it.
         const auto t_start = std::chrono::steady_clock::now();
         { struct stat st_in; g_input_is_stream = stat(bam_path.c_str(), &st_in) == 0 && !S_ISREG(st_in.st_mode); }
+        // the input's format by its content (a stream is sniffed where it is opened, below)
+        const InputFormat file_fmt = g_input_is_stream ? InputFormat::Unknown : sniff_file(bam_path);
         auto feeder_cpu_threads = [] {
             const int spare = effective_cpus() - 4;
             return getenv("RSQC_DECODE_CPU_THREADS") ? atoi(getenv("RSQC_DECODE_CPU_THREADS")) : (spare >= 4 ? spare : 0);
@@ -406,7 +413,7 @@ int main(int argc, char **argv) {
         const bool feeder_prepin = !(getenv("RSQC_FEED_PREPIN") && !atoi(getenv("RSQC_FEED_PREPIN")));
         std::unique_ptr<BgzfFeeder> early_feed;
         std::future<bool> early_feed_ready;
-        if (device_decode_wanted() && feeder_prepin && o.gpus <= 1 && !getenv("RSQC_GPUS") && !getenv("RSQC_GPU_LIST")) {
+        if (device_decode_wanted() && file_fmt == InputFormat::Bam && feeder_prepin && o.gpus <= 1 && !getenv("RSQC_GPUS") && !getenv("RSQC_GPU_LIST")) {
             early_feed.reset(new BgzfFeeder());
             BgzfFeeder *ef = early_feed.get();
             const int ct = feeder_cpu_threads();
@@ -457,14 +464,64 @@ int main(int argc, char **argv) {
         std::vector<std::string> bam_contigs;
         uint64_t first_voff = 0;
         bool bam_open = false;
+        // SAM input (plain or BGZF-compressed): the header's @SQ lines are read here, the text goes to the device SAM stages
+        InputFormat in_fmt = file_fmt;
+        std::string reader_path = bam_path;                                   // what the host BAM reader opens
+        std::unique_ptr<SamTextFeeder> sam_feed;
+        if (g_input_is_stream) {
+            // a FIFO / stdin: its first bytes are read to tell the format and stay the first chunk's; a BAM is handed on to the
+            // host reader through a pipe of this process that replays them
+            sam_feed.reset(new SamTextFeeder());
+            if (!sam_feed->open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
+            const std::vector<uint8_t> &first = sam_feed->peek(1 << 16);
+            in_fmt = sniff_format(first.data(), first.size());
+            if (in_fmt == InputFormat::Bam || in_fmt == InputFormat::Unknown) {
+                int pfd[2];
+                if (pipe(pfd) != 0) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
+                signal(SIGPIPE, SIG_IGN);
+                const int src = sam_feed->release_fd();
+                std::thread([src, pfd, head = sam_feed->peek(0)]() {
+                    auto put = [&](const uint8_t *b, size_t n) { while (n) { const ssize_t w = write(pfd[1], b, n); if (w <= 0) return false; b += w; n -= (size_t)w; } return true; };
+                    bool ok = put(head.data(), head.size());
+                    std::vector<uint8_t> buf(1 << 20);
+                    while (ok) { const ssize_t g = read(src, buf.data(), buf.size()); if (g <= 0) break; ok = put(buf.data(), (size_t)g); }
+                    close(pfd[1]); close(src);
+                }).detach();
+                reader_path = "/dev/fd/" + std::to_string(pfd[0]);
+                sam_feed.reset();
+                in_fmt = InputFormat::Bam;
+            }
+        }
+        if (in_fmt == InputFormat::PlainGzip) {
+            cerr << "Unable to open BAM file: " << bam_path << " (gzip-compressed but not BGZF: recompress it with bgzip)" << endl; return 10;
+        }
+        if (in_fmt == InputFormat::SamBgzf && g_input_is_stream) {
+            cerr << "Unable to open BAM file: " << bam_path << " (BGZF-compressed SAM is read from a regular file only: decompress it into the pipe)" << endl; return 10;
+        }
+        const bool sam_input = in_fmt == InputFormat::SamText || in_fmt == InputFormat::SamBgzf;
+        if (sam_input) {
+            SamHeader hdr;
+            if (sam_feed) {
+                bool complete = false;
+                for (size_t want = 1 << 16;; want *= 2) {
+                    const auto &hd = sam_feed->peek(want);
+                    hdr = SamHeader{};
+                    parse_sam_header((const char *)hd.data(), hd.size(), hdr, complete);
+                    if (complete || hd.size() < want) break;
+                }
+            } else if (!read_sam_header(bam_path, hdr)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
+            bam_contigs = hdr.names;
+            if (o.verbosity > 1) cout << "Input: " << input_format_name(in_fmt) << " (" << hdr.names.size() << " @SQ lines), parsed on the GPU" << endl;
+        }
         auto open_host_reader = [&]() -> bool {
             if (bam_open) return true;
-            if (!bam.open(bam_path)) return false;
+            if (!bam.open(reader_path)) return false;
             bam.set_tags(o.chimeric_tag, o.tags);
             bam_open = true;
             return true;
         };
-        if (device_decode_wanted()) {
+        if (sam_input) {
+        } else if (device_decode_wanted()) {
             BgzfFeeder probe;
             if (!probe.open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
             try { first_voff = probe.first_record_voffset(&bam_contigs); }
@@ -486,7 +543,7 @@ int main(int argc, char **argv) {
             int want = o.gpus > 0 ? o.gpus : (getenv("RSQC_GPUS") ? atoi(getenv("RSQC_GPUS")) : 1);
             if (const char *e = getenv("RSQC_GPU_LIST")) { for (const char *q = e; *q;) { devices.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q) ++q; } }
             else for (int k = 0; k < std::max(1, want); ++k) devices.push_back(P.device + k);
-            if (devices.size() > 1 && !bam.load_index(bam_path + ".bai")) {
+            if (devices.size() > 1 && (sam_input || !bam.load_index(bam_path + ".bai"))) {       // (SAM has no index)
                 cerr << "Warning: sharding over " << devices.size() << " GPUs needs the BAM index " << bam_path << ".bai; running on one GPU" << endl;
                 devices.resize(1);
             }
@@ -573,10 +630,10 @@ int main(int argc, char **argv) {
         }
 
         // device decode needs exact range ends from the index when the file is sharded
-        bool device_decode = device_decode_wanted();
+        bool device_decode = device_decode_wanted() && !sam_input;
         if (device_decode && shards.size() > 1)
             for (auto &r : bam.index()) if (r.present && !r.end) device_decode = false;
-        if (!device_decode && shards.size() == 1 && !open_host_reader()) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
+        if (!sam_input && !device_decode && shards.size() == 1 && !open_host_reader()) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
         if (device_decode && !(getenv("RSQC_DECODE_PRERESERVE") && !atoi(getenv("RSQC_DECODE_PRERESERVE")))) {
             // the device's window buffers are set up before the loop, like the host path's page-locked batches below
             struct stat st{};
@@ -664,6 +721,69 @@ int main(int argc, char **argv) {
                 double reduce_ms = 0.0; rsqc_group_info(xgroup, nullptr, nullptr, &reduce_ms, nullptr);
                 cout << " records); shards summed by " << (used_rccl ? "RCCL ncclReduce" : "peer copies") << " in " << reduce_ms << " ms (group set-up " << group_init_ms << " ms, outside the window)" << endl;
             }
+        } else if (sam_input) {
+            // ---- one GPU, SAM text: the host reads the file (plain) or frames its BGZF blocks, the device does the rest
+            rsqc_decode_info di{};
+            std::vector<const char *> names;
+            for (auto &nm : bam_contigs) names.push_back(nm.c_str());
+            auto on_window = [&](const rsqc_decode_window &w) {
+                bool revisit = false;
+                for (uint32_t k = 0; k < w.n_runs; ++k) {
+                    const int32_t t = w.run_tid[k];
+                    if (t < 0 || (!visit.empty() && visit.back() == t)) continue;
+                    if (std::find(visit.begin(), visit.end(), t) != visit.end()) revisit = true;
+                    visit.push_back(t);
+                    if (o.has_fasta && (size_t)t < in_fasta.size() && !in_fasta[(size_t)t])
+                        cerr << "Warning: Provided Fasta does not contain chromosome " << ann.contig_names[(size_t)t]
+                             << ". No GC statistics will be collected for this chromosome" << endl;
+                }
+                if (revisit && !warned_unsorted) {
+                    cerr << "Warning: The input bam does not appear to be sorted. An unsorted bam will yield incorrect results" << endl;
+                    warned_unsorted = true;
+                }
+                alignmentCount += w.n_records;
+                if (o.verbosity > 1) cout << "Alignments processed: " << alignmentCount << endl;
+            };
+            if (in_fmt == InputFormat::SamBgzf) {
+                BgzfFeeder feed;
+                if (!feed.open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
+                feed.read_threads = std::max(1, std::min(8, effective_cpus() / 2));
+                rc = decode_range(gpu, feed, decode_params(o, n_ref_bam, 0), 0, 0, di, on_window, names.data());
+            } else {
+                if (!sam_feed) {
+                    sam_feed.reset(new SamTextFeeder());
+                    if (!sam_feed->open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
+                }
+                // (RSQC_SAM_CHUNK: bytes of text per call; the tests use small values so that lines straddle many calls)
+                const size_t chunk = getenv("RSQC_SAM_CHUNK") ? (size_t)atoll(getenv("RSQC_SAM_CHUNK")) : (size_t)256 << 20;
+                rsqc_decode_params dp = decode_params(o, n_ref_bam, 0);
+                dp.pipelined = 1;
+                dp.reserve_inflated_bytes = chunk + (1u << 20);
+                rc = rsqc_decode_begin_sam(gpu, &dp, names.data());
+                if (rc == RSQC_OK) {
+                    sam_feed->start(chunk);
+                    while (SamTextFeeder::Chunk *ch = sam_feed->next()) {
+                        rsqc_decode_window w{};
+                        rc = rsqc_decode_submit_text(gpu, ch->data, ch->bytes, &w);
+                        if (rc != RSQC_OK) break;
+                        if (w.n_records) on_window(w);
+                    }
+                    if (rc != RSQC_OK) { rsqc_decode_info dropped{}; (void)rsqc_decode_end(gpu, &dropped); }
+                    else {
+                        if (!sam_feed->error().empty()) throw std::runtime_error(sam_feed->error());
+                        rc = rsqc_decode_end(gpu, &di);
+                        if (rc == RSQC_OK && di.last.n_records) on_window(di.last);
+                    }
+                }
+            }
+            if (rc == RSQC_ERR_INPUT) throw std::runtime_error(rsqc_last_error(gpu));
+            if (rc == RSQC_OK) {
+                if (o.verbosity) for (int k = 0; k < di.n_bad_refid && k < 64; ++k) cerr << "Unrecognized RefID on alignment: " << di.bad_refid[k] << endl;
+                if (di.unsorted && !warned_unsorted) {
+                    cerr << "Warning: The input bam does not appear to be sorted. An unsorted bam will yield incorrect results" << endl;
+                    warned_unsorted = true;
+                }
+            }
         } else if (device_decode) {
             // ---- one GPU, device decode: the host reads the file and frames the BGZF blocks, nothing else
             rsqc_decode_info di{};
@@ -742,7 +862,8 @@ int main(int argc, char **argv) {
             const double secs = std::chrono::duration<double>(tb1 - tb0).count();
             cout << "Time Elapsed: " << secs << "; Alignments processed: " << alignmentCount << endl;
             if (o.verbosity > 1) cout << "Average Reads/Sec: " << (double)alignmentCount / secs << endl;
-            if (o.verbosity > 1 && device_decode) cout << "(decode: BGZF inflate and record parsing on the GPU)" << endl;
+            if (o.verbosity > 1 && sam_input) cout << "(decode: " << (in_fmt == InputFormat::SamBgzf ? "BGZF inflate and SAM text parsing" : "SAM text") << " on the GPU)" << endl;
+            else if (o.verbosity > 1 && device_decode) cout << "(decode: BGZF inflate and record parsing on the GPU)" << endl;
             else if (o.verbosity > 1 && shards.size() == 1) cout << "(decode threads: " << bam.inflate_threads() << " inflate + " << bam.parse_threads() << " parse)" << endl;
             cout << "Estimating library complexity..." << endl;
             cout << "Generating report" << endl;

@@ -22,6 +22,7 @@
 #include "rsqc_device.h"
 #include "rsqc_index.h"
 #include "rsqc_decode.h"
+#include "rsqc_sam.h"
 
 // Knobs that make the library SKIP work (wrong or incomplete results) exist only in the diagnostic build (`make prof`,
 // -DRSQC_K1_PROF): the product library does not read them.
@@ -132,6 +133,17 @@ struct DecodeState {
     hipStream_t copy_stream = nullptr; hipEvent_t ev_copy = nullptr;
     std::vector<int32_t> run_tid;      // contig segments of the last window
     rsqc_batch last{};                 // the last window's batch (device pointers): rsqc_decode_window::device_batch
+    // a SAM text stream (rsqc_decode_begin_sam): the stages of rsqc_sam.hip instead of the BAM framing and parsing
+    bool sam = false;
+    size_t sam_cap = 0;                // the out_cap the SAM buffers below were sized for
+    uint32_t sam_rec_cap = 0;
+    DevBuf sam_ebits, sam_tbits, sam_segcnt, sam_segk0, sam_rtid, sam_nops, sam_st, sam_sc, sam_scratch, sam_slots, sam_names;
+    SamRefTable sam_refs{};
+    SamStatus *h_sam_st = nullptr;     // page-locked
+    SamWindow pend_s{};
+    uint64_t sam_line0 = 1;            // line number of the first byte of the next window (header lines counted)
+    std::vector<std::string> sam_ref_names;
+    std::vector<int32_t> sam_last_runs;  // rsqc_decode_end: runs of the last window and of the one that ended the last line
 };
 
 }  // namespace
@@ -1641,7 +1653,8 @@ int rsqc_reset_timing(rsqc_ctx *c) {
 
 // ---- device-side BAM decode ---------------------------------------------------------------------------------------
 namespace { int decode_reserve(rsqc_ctx *c, size_t out_bytes, size_t comp_bytes, size_t n_blocks); }
-int rsqc_decode_begin(rsqc_ctx *c, const rsqc_decode_params *p) {
+namespace {
+int decode_begin_common(rsqc_ctx *c, const rsqc_decode_params *p, bool sam) {
     if (!c || !p || p->n_ref < 0) return RSQC_ERR_ARG;
     if (!c->have_ann) return fail(c, RSQC_ERR_ARG, "rsqc_set_annotation must precede rsqc_decode_begin");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1654,6 +1667,7 @@ int rsqc_decode_begin(rsqc_ctx *c, const rsqc_decode_params *p) {
     D.next_file_index = p->file_index_base; D.records = 0; D.tail = 0;
     D.unsorted = false; D.n_bad = 0; D.bad_names.clear();
     D.pipelined = p->pipelined != 0; D.pending = false; D.slot = 0;
+    D.sam = sam; D.sam_line0 = 1;
     if (!D.copy_stream) { HIP_TRY(c, hipStreamCreateWithFlags(&D.copy_stream, hipStreamNonBlocking)); HIP_TRY(c, hipEventCreateWithFlags(&D.ev_copy, hipEventDisableTiming)); }
     D.profile = getenv("RSQC_DECODE_PROFILE") != nullptr;
     D.ms_copy = D.ms_inflate = D.ms_parse = D.ms_call = 0; D.prof_in = D.prof_out = D.prof_calls = 0;
@@ -1669,6 +1683,41 @@ int rsqc_decode_begin(rsqc_ctx *c, const rsqc_decode_params *p) {
     }
     D.active = true;
     return RSQC_OK;
+}
+}  // namespace
+int rsqc_decode_begin(rsqc_ctx *c, const rsqc_decode_params *p) { return decode_begin_common(c, p, false); }
+
+int rsqc_decode_begin_sam(rsqc_ctx *c, const rsqc_decode_params *p, const char *const *ref_names) {
+    if (!c || !p || p->n_ref < 0 || (p->n_ref > 0 && !ref_names)) return RSQC_ERR_ARG;
+    if (!c->have_ann) return fail(c, RSQC_ERR_ARG, "rsqc_set_annotation must precede rsqc_decode_begin_sam");
+    HIP_TRY(c, hipSetDevice(c->device));
+    DecodeState &D = c->dec;
+    // the @SQ names: an open-addressed table on their FNV-1a hash, at least twice as many slots as names (first name wins)
+    D.sam_ref_names.assign(ref_names, ref_names + p->n_ref);
+    uint32_t slots = 16;
+    while (slots < 2u * (uint32_t)p->n_ref) slots <<= 1;
+    std::vector<SamRefSlot> tab(slots, SamRefSlot{0, 0, 0, -1, 0});
+    std::vector<uint8_t> names;
+    for (int32_t r = 0; r < p->n_ref; ++r) {
+        const std::string &nm = D.sam_ref_names[(size_t)r];
+        const uint64_t h = bam_qname_hash((const uint8_t *)nm.data(), (uint32_t)nm.size());
+        uint32_t k = (uint32_t)h & (slots - 1);
+        bool dup = false;
+        for (; tab[k].idx >= 0; k = (k + 1) & (slots - 1))
+            if (tab[k].hash == h && tab[k].len == nm.size() && !memcmp(names.data() + tab[k].off, nm.data(), nm.size())) { dup = true; break; }
+        if (dup) continue;
+        tab[k] = SamRefSlot{h, (uint32_t)names.size(), (uint32_t)nm.size(), r, 0};
+        names.insert(names.end(), nm.begin(), nm.end());
+    }
+    int rc;
+    if ((rc = dev_alloc(c, D.sam_slots, tab.size() * sizeof(SamRefSlot), false)) || (rc = dev_alloc(c, D.sam_names, names.size() + 16, false)) ||
+        (rc = dev_alloc(c, D.sam_st, sizeof(SamStatus), false)) || (rc = dev_alloc(c, D.sam_sc, sizeof(SamCarry), true))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(D.sam_slots.p, tab.data(), tab.size() * sizeof(SamRefSlot), hipMemcpyHostToDevice, c->stream));
+    if (!names.empty()) HIP_TRY(c, hipMemcpyAsync(D.sam_names.p, names.data(), names.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    D.sam_refs = SamRefTable{(const SamRefSlot *)D.sam_slots.p, (const uint8_t *)D.sam_names.p, slots - 1, p->n_ref};
+    if (!D.h_sam_st) HIP_TRY(c, hipHostMalloc((void **)&D.h_sam_st, sizeof(SamStatus), hipHostMallocDefault));
+    return decode_begin_common(c, p, true);
 }
 
 namespace {
@@ -1687,8 +1736,8 @@ int decode_reserve(rsqc_ctx *c, size_t out_bytes, size_t comp_bytes, size_t n_bl
         if (D.h_blocks) (void)hipHostFree(D.h_blocks);
         HIP_TRY(c, hipHostMalloc((void **)&D.h_blocks, 2 * D.blk_cap * sizeof(DevBgzfBlock), hipHostMallocDefault));
     }
-    if (out_bytes <= D.out_cap) return 0;
-    const size_t cap = std::max<size_t>(out_bytes + out_bytes / 8, 64u << 20);
+    if (out_bytes <= D.out_cap && (!D.sam || D.sam_cap == D.out_cap)) return 0;
+    const size_t cap = std::max<size_t>(std::max<size_t>(out_bytes + out_bytes / 8, 64u << 20), D.out_cap);
     const size_t W = (size_t)D.head + cap;
     // the window buffer keeps the carried-over bytes
     DevBuf nu;
@@ -1696,21 +1745,46 @@ int decode_reserve(rsqc_ctx *c, size_t out_bytes, size_t comp_bytes, size_t n_bl
     if (D.tail) HIP_TRY(c, hipMemcpyAsync((char *)nu.p + D.head - D.tail, (char *)D.ubuf.p + D.head - D.tail, D.tail, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     D.ubuf.release(); D.ubuf = nu;
-    const size_t n_seg = W / DEC_SEG_BYTES + 4, n_rec = W / 36 + 4;
+    // (a SAM line is at least SAM_MIN_LINE bytes, a BAM record 36)
+    const size_t n_seg = W / DEC_SEG_BYTES + 4, n_rec = W / (D.sam ? SAM_MIN_LINE : 36) + 4;
     if ((rc = dev_alloc(c, D.seg, n_seg * sizeof(BamSegment), false)) || (rc = dev_alloc(c, D.seg_rec0, n_seg * 4, false)) ||
         (rc = dev_alloc(c, D.seg_ops0, n_seg * 4, false)) || (rc = dev_alloc(c, D.rec_off, n_rec * 4, false)) ||
         (rc = dev_alloc(c, D.ops_at, n_rec * 4, false)) || (rc = dev_alloc(c, D.mark, n_rec, false)) ||
         (rc = dev_alloc(c, D.core, n_rec * 16 + 64, false)) || (rc = dev_alloc(c, D.aux, n_rec * 16 + 64, false)) || (rc = dev_alloc(c, D.qh2, n_rec * 4 + 64, false)) ||
-        (rc = dev_alloc(c, D.cigar, W + 256, false)) || (rc = dev_alloc(c, D.seg_tid, n_rec * 4 + 64, false)) ||
+        (rc = dev_alloc(c, D.cigar, D.sam ? std::max<size_t>(W + 256, (size_t)sam_caps(W).cigar_alloc * 4) : W + 256, false)) ||
+        (rc = dev_alloc(c, D.seg_tid, n_rec * 4 + 64, false)) ||
         (rc = dev_alloc(c, D.seg_start, (n_rec + 1) * 8 + 64, false)) || (rc = dev_alloc(c, D.wide_index, n_rec * 8 + 64, false)) ||
         (rc = dev_alloc(c, D.wide_nm, n_rec * 4 + 64, false)) || (rc = dev_alloc(c, D.wide_lq, n_rec * 4 + 64, false)) ||
         (rc = dev_alloc(c, D.wide_nc, n_rec * 4 + 64, false))) return rc;
     D.out_cap = cap;
+    if (D.sam) {
+        const size_t n_words = W / 64 + 8, n_sseg = n_words / SAM_SEG_WORDS + 2;
+        if ((rc = dev_alloc(c, D.sam_ebits, n_words * 8, false)) || (rc = dev_alloc(c, D.sam_tbits, n_words * 8, false)) ||
+            (rc = dev_alloc(c, D.sam_segcnt, n_sseg * 4, false)) || (rc = dev_alloc(c, D.sam_segk0, n_sseg * 4, false)) ||
+            (rc = dev_alloc(c, D.sam_rtid, n_rec * 4 + 64, false)) || (rc = dev_alloc(c, D.sam_nops, n_rec * 4 + 64, false)) ||
+            (rc = dev_alloc(c, D.sam_scratch, sam_scratch_words((uint32_t)n_rec, (uint32_t)n_sseg) * 4, false))) return rc;
+        D.sam_cap = cap; D.sam_rec_cap = sam_caps(W).rec_alloc;
+    }
     return 0;
 }
 }  // namespace
 
 namespace {
+// a SAM window the device stages refused: the first malformed line, found again on the host with the same functions, and its
+// line number in the stream (rare path: the window's text is copied back)
+void sam_window_error(rsqc_ctx *c, const DecodeWindow &W, std::string &msg) {
+    DecodeState &D = c->dec;
+    std::vector<uint8_t> t((size_t)(W.end - W.start) + 1, 0);
+    if (W.end > W.start && hipMemcpy(t.data(), (const char *)D.ubuf.p + W.start, W.end - W.start, hipMemcpyDeviceToHost) != hipSuccess)
+        { msg = "malformed SAM line (the window could not be read back)"; return; }
+    uint64_t line = 0; uint32_t code = 0;
+    if (sam_find_bad_line(t.data(), W.end - W.start, D.records > 0, D.tags, D.sam_line0, line, code)) {
+        msg = "malformed SAM line " + std::to_string(line) + ": " + sam_error_text(code);
+        return;
+    }
+    msg = "malformed SAM line (window from line " + std::to_string(D.sam_line0) + ")";
+}
+
 // second half of a call: wait for the window's kernels, read its summary, submit its records as a batch, park what is left
 int decode_finish(rsqc_ctx *c, rsqc_decode_window *out) {
     DecodeState &D = c->dec;
@@ -1732,10 +1806,24 @@ int decode_finish(rsqc_ctx *c, rsqc_decode_window *out) {
         c->sticky = RSQC_ERR_INPUT;
         return fail(c, RSQC_ERR_INPUT, "BGZF inflate failed (corrupt block " + std::to_string((S.inflate_fail >> 4) - 1) + " of the call, code " + std::to_string(S.inflate_fail & 15u) + ")");
     }
-    if (S.status & DEC_ST_BAD_RECORD) { c->sticky = RSQC_ERR_INPUT; return fail(c, RSQC_ERR_INPUT, "bad BAM record"); }
+    if (S.status & DEC_ST_BAD_RECORD) {
+        c->sticky = RSQC_ERR_INPUT;
+        if (!D.sam) return fail(c, RSQC_ERR_INPUT, "bad BAM record");
+        std::string msg;
+        sam_window_error(c, W, msg);
+        return fail(c, RSQC_ERR_INPUT, msg);
+    }
     // the reference's stderr diagnostics
     if (S.unsorted) D.unsorted = true;
-    for (uint32_t k = 0; k < S.n_bad && k < DEC_MAX_BAD && D.bad_names.size() < DEC_MAX_BAD; ++k) {
+    for (uint32_t k = 0; D.sam && k < S.n_bad && k < DEC_MAX_BAD && D.bad_names.size() < DEC_MAX_BAD; ++k) {
+        char raw[256] = {0};                                             // (a SAM line: the name is its first field)
+        const size_t room = std::min<size_t>(sizeof raw, (size_t)W.end - S.bad_off[k]);
+        HIP_TRY(c, hipMemcpy(raw, (const char *)D.ubuf.p + S.bad_off[k], room, hipMemcpyDeviceToHost));
+        size_t l = 0;
+        while (l < room && raw[l] != '\t') ++l;
+        D.bad_names.emplace_back(raw, l);
+    }
+    for (uint32_t k = 0; !D.sam && k < S.n_bad && k < DEC_MAX_BAD && D.bad_names.size() < DEC_MAX_BAD; ++k) {
         uint8_t raw[36 + 256] = {0};
         const size_t room = std::min<size_t>(sizeof raw, (size_t)W.end - S.bad_off[k]);
         HIP_TRY(c, hipMemcpy(raw, (const char *)D.ubuf.p + S.bad_off[k], room, hipMemcpyDeviceToHost));
@@ -1750,6 +1838,7 @@ int decode_finish(rsqc_ctx *c, rsqc_decode_window *out) {
         HIP_TRY(c, hipMemcpyAsync(D.tailtmp.p, (const char *)D.ubuf.p + S.consumed_end, left, hipMemcpyDeviceToDevice, c->stream));
         if (left <= D.head) HIP_TRY(c, hipMemcpyAsync((char *)D.ubuf.p + D.head - left, D.tailtmp.p, left, hipMemcpyDeviceToDevice, c->stream));
     }
+    if (D.sam) D.sam_line0 += D.h_sam_st->n_nl;
     D.run_tid.assign(S.n_seg, 0);
     if (S.n_seg) HIP_TRY(c, hipMemcpy(D.run_tid.data(), D.seg_tid.p, (size_t)S.n_seg * 4, hipMemcpyDeviceToHost));
     if (out) { out->n_records = S.n_rec; out->n_runs = S.n_seg; out->run_tid = D.run_tid.data(); out->device_batch = rsqc_batch{}; }
@@ -1784,6 +1873,10 @@ int decode_finish(rsqc_ctx *c, rsqc_decode_window *out) {
 }
 }  // namespace
 
+namespace {
+int decode_enqueue(rsqc_ctx *c, const void *compressed, uint64_t compressed_bytes, const rsqc_bgzf_block *blocks, uint32_t n_blocks, uint32_t n_gpu,
+                   uint64_t total, uint64_t raw_total, uint64_t raw_src, uint32_t skip_bytes, uint64_t limit_bytes, rsqc_decode_window *out);
+}
 int rsqc_decode_submit(rsqc_ctx *c, const void *compressed, uint64_t compressed_bytes, const rsqc_bgzf_block *blocks, uint32_t n_blocks,
                        uint32_t skip_bytes, uint64_t limit_bytes, rsqc_decode_window *out) {
     if (!c || (!compressed && compressed_bytes) || (!blocks && n_blocks)) return RSQC_ERR_ARG;
@@ -1807,6 +1900,29 @@ int rsqc_decode_submit(rsqc_ctx *c, const void *compressed, uint64_t compressed_
         } else if (n_gpu != n_blocks) return fail(c, RSQC_ERR_ARG, "inflated blocks must form one run at the end of the call");
         total += b.out_bytes;
     }
+    return decode_enqueue(c, compressed, compressed_bytes, blocks, n_blocks, n_gpu, total, raw_total, n_gpu < n_blocks ? blocks[n_gpu].in_offset : 0,
+                          skip_bytes, limit_bytes, out);
+}
+
+int rsqc_decode_submit_text(rsqc_ctx *c, const void *text, uint64_t bytes, rsqc_decode_window *out) {
+    if (!c || (!text && bytes)) return RSQC_ERR_ARG;
+    if (c->sticky) return c->sticky;
+    DecodeState &D = c->dec;
+    if (!D.active) return fail(c, RSQC_ERR_ARG, "rsqc_decode_begin_sam must precede rsqc_decode_submit_text");
+    if (!D.sam) return fail(c, RSQC_ERR_ARG, "rsqc_decode_submit_text needs a SAM stream (rsqc_decode_begin_sam)");
+    if (out) { out->n_records = 0; out->n_runs = 0; out->run_tid = nullptr; out->device_batch = rsqc_batch{}; }
+    D.last = rsqc_batch{};
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the text crosses PCIe like a run of caller-inflated blocks: staged on the copy stream, then moved into the window
+    return decode_enqueue(c, text, bytes, nullptr, 0, 0, bytes, bytes, 0, 0, 0, out);
+}
+
+namespace {
+// the second half of rsqc_decode_submit / rsqc_decode_submit_text: `total` bytes for the window, of which the blocks [0, n_gpu)
+// are inflated on the device and the last raw_total bytes arrive as they are, at raw_src of `compressed`
+int decode_enqueue(rsqc_ctx *c, const void *compressed, uint64_t compressed_bytes, const rsqc_bgzf_block *blocks, uint32_t n_blocks, uint32_t n_gpu,
+                   uint64_t total, uint64_t raw_total, uint64_t raw_src, uint32_t skip_bytes, uint64_t limit_bytes, rsqc_decode_window *out) {
+    DecodeState &D = c->dec;
     if (total + D.head > (1ull << 31)) return fail(c, RSQC_ERR_ARG, "too much inflated data in one rsqc_decode_submit (2 GiB with the bytes carried over)");
     if (skip_bytes > total) return fail(c, RSQC_ERR_ARG, "skip_bytes beyond the inflated data");
     int rc;
@@ -1861,7 +1977,7 @@ int rsqc_decode_submit(rsqc_ctx *c, const void *compressed, uint64_t compressed_
     const bool one_pass = force_one_pass >= 0 ? force_one_pass != 0 : total < 5 * (uint64_t)std::max<uint64_t>(compressed_bytes - raw_total, 1);
     launch_bgzf_inflate(c->stream, dcomp, dblk, n_gpu, (uint8_t *)D.ubuf.p, (DecodeSummary *)D.sum.p, one_pass);
     if (raw_total)                                                      // the caller-inflated run: staged with the file bytes, now moved into the window
-        HIP_TRY(c, hipMemcpyAsync((char *)D.ubuf.p + raw_at, dcomp + blocks[n_gpu].in_offset, (size_t)raw_total, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync((char *)D.ubuf.p + raw_at, dcomp + raw_src, (size_t)raw_total, hipMemcpyDeviceToDevice, c->stream));
     const bool limited = limit_bytes && limit_bytes < total;
     DecodeWindow &W = D.pend_w;
     W = DecodeWindow{};
@@ -1877,9 +1993,28 @@ int rsqc_decode_submit(rsqc_ctx *c, const void *compressed, uint64_t compressed_
     W.wide_index = (uint64_t *)D.wide_index.p; W.wide_nm = (int32_t *)D.wide_nm.p; W.wide_lq = (int32_t *)D.wide_lq.p; W.wide_nc = (uint32_t *)D.wide_nc.p;
     W.sum = (DecodeSummary *)D.sum.p; W.carry = (DecodeCarry *)D.carry.p; W.tags = D.tags;
     if (D.profile) HIP_TRY(c, hipEventRecord(D.pe[2], c->stream));
+    if (D.sam) {
+        SamWindow &S = D.pend_s;
+        S = SamWindow{};
+        S.W = W;
+        S.base = W.start & ~63u;
+        S.n_words = (W.end - S.base + 63u) / 64u;
+        S.n_seg = (S.n_words + SAM_SEG_WORDS - 1) / SAM_SEG_WORDS;
+        S.rec_cap = sam_window_rec_cap(D.sam_rec_cap, W.end - W.start, D.records > 0);
+        S.cigar_cap = (uint32_t)std::min<size_t>(D.cigar.bytes / 4, 0xFFFFFFF0u);
+        S.ebits = (uint64_t *)D.sam_ebits.p; S.tbits = (uint64_t *)D.sam_tbits.p;
+        S.seg_cnt = (uint32_t *)D.sam_segcnt.p; S.seg_k0 = (uint32_t *)D.sam_segk0.p;
+        S.rtid = (int32_t *)D.sam_rtid.p; S.nops = (uint32_t *)D.sam_nops.p;
+        S.refs = D.sam_refs; S.st = (SamStatus *)D.sam_st.p; S.sc = (SamCarry *)D.sam_sc.p;
+        HIP_TRY(c, hipMemsetAsync(D.sam_st.p, 0, sizeof(SamStatus), c->stream));
+        HIP_TRY(c, hipMemsetAsync(&S.st->hdr_end, 0xff, 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(&S.st->first_bad, 0xff, 4, c->stream));
+        launch_sam_window(c->stream, S, (uint32_t *)D.sam_scratch.p);
+    } else
     launch_decode_window(c->stream, W, (uint32_t *)D.scratch.p);
     if (D.profile) HIP_TRY(c, hipEventRecord(D.pe[3], c->stream));
     HIP_TRY(c, hipMemcpyAsync(D.h_sum, D.sum.p, sizeof(DecodeSummary), hipMemcpyDeviceToHost, c->stream));
+    if (D.sam) HIP_TRY(c, hipMemcpyAsync(D.h_sam_st, D.sam_st.p, sizeof(SamStatus), hipMemcpyDeviceToHost, c->stream));
     D.pending = true; D.pend_limited = limited;
     if (D.profile) { D.prof_in += compressed_bytes; D.prof_out += total; }
     // the caller's buffer is free again once the copy is through (the copy engine works beside the kernels)
@@ -1887,14 +2022,30 @@ int rsqc_decode_submit(rsqc_ctx *c, const void *compressed, uint64_t compressed_
     if (!D.pipelined) return decode_finish(c, out);
     return RSQC_OK;
 }
+}  // namespace
 
 int rsqc_decode_end(rsqc_ctx *c, rsqc_decode_info *out) {
     if (!c) return RSQC_ERR_ARG;
     DecodeState &D = c->dec;
     if (!D.active) return fail(c, RSQC_ERR_ARG, "rsqc_decode_begin must precede rsqc_decode_end");
-    D.active = false;
     rsqc_decode_window last{};
-    if (D.pending) { const int rcf = decode_finish(c, &last); if (rcf) return rcf; }
+    if (D.pending) { const int rcf = decode_finish(c, &last); if (rcf) { D.active = false; return rcf; } }
+    if (D.sam && D.tail && !c->sticky) {
+        // a last line without its '\n' (htslib reads it): ended here, in one more (non-pipelined) window
+        D.sam_last_runs.assign(last.run_tid, last.run_tid + last.n_runs);
+        const uint64_t na = last.n_records;
+        const bool pl = D.pipelined;
+        D.pipelined = false;
+        rsqc_decode_window b{};
+        const int rcb = rsqc_decode_submit_text(c, "\n", 1, &b);
+        D.pipelined = pl;
+        if (rcb) { D.active = false; return rcb; }
+        D.sam_last_runs.insert(D.sam_last_runs.end(), b.run_tid, b.run_tid + b.n_runs);
+        last = b;
+        last.n_records += na; last.n_runs = (uint32_t)D.sam_last_runs.size(); last.run_tid = D.sam_last_runs.data();
+        if (pl || na) last.device_batch = rsqc_batch{};
+    }
+    D.active = false;
     if (out) out->last = last;
     if (D.profile)
         fprintf(stderr, "[decode] %llu calls, %.1f MB in, %.1f MB inflated: copy %.1f ms, inflate %.1f ms (%.2f GB/s out), frame+parse %.1f ms, in the calls %.1f ms of %.1f ms between begin and end\n",
@@ -1907,7 +2058,11 @@ int rsqc_decode_end(rsqc_ctx *c, rsqc_decode_info *out) {
         out->n_bad_refid = (int32_t)std::min<uint64_t>(D.n_bad, 0x7fffffff);
         out->bad_refid = D.bad_ptrs.data();
     }
-    if (D.tail) { D.tail = 0; return fail(c, RSQC_ERR_INPUT, "truncated BAM record"); }
+    if (D.tail) {
+        D.tail = 0;
+        if (D.sam && c->sticky) return c->sticky;                      // (the malformed line's message stays the last error)
+        return fail(c, RSQC_ERR_INPUT, D.sam ? "truncated SAM line" : "truncated BAM record");
+    }
     return RSQC_OK;
 }
 

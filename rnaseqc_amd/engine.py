@@ -68,6 +68,8 @@ def load_library():
         lib.rsqc_decode_begin.argtypes = [vp, C.POINTER(abi.DecodeParams)]
         lib.rsqc_decode_submit.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(abi.DecodeWindow)]
         lib.rsqc_decode_end.argtypes = [vp, C.POINTER(abi.DecodeInfo)]
+        lib.rsqc_decode_begin_sam.argtypes = [vp, C.POINTER(abi.DecodeParams), C.POINTER(C.c_char_p)]
+        lib.rsqc_decode_submit_text.argtypes = [vp, vp, C.c_uint64, C.POINTER(abi.DecodeWindow)]
         _lib = lib
     return _lib
 
@@ -78,7 +80,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_reset_timing", "rsqc_device_accumulators", "rsqc_device_vectors", "rsqc_shard_summary", "rsqc_reduce_peer", "rsqc_reduce_group",
     "rsqc_group_create", "rsqc_group_reduce", "rsqc_group_info", "rsqc_group_destroy", "rsqc_refresh_results", "rsqc_finalize_device", "rsqc_host_alloc", "rsqc_host_free", "rsqc_strerror",
     "rsqc_last_error", "rsqc_counter_name", "rsqc_version", "rsqc_qname_hash", "rsqc_qname_hash2",
-    "rsqc_decode_begin", "rsqc_decode_submit", "rsqc_decode_end",
+    "rsqc_decode_begin", "rsqc_decode_submit", "rsqc_decode_end", "rsqc_decode_begin_sam", "rsqc_decode_submit_text",
 ]
 
 
@@ -157,7 +159,9 @@ class Engine:
         self._check(self._l.rsqc_wait(self._h))
 
     # ---- device-side BAM decode (rsqc_decode_*) -----------------------------------------------------------------
-    def decode_begin(self, n_ref, ch_tag="ch", filter_tags=(), file_index_base=0, pipelined=False, reserve=0):
+    def decode_begin(self, n_ref, ch_tag="ch", filter_tags=(), file_index_base=0, pipelined=False, reserve=0, ref_names=None):
+        """ref_names (the SAM header's @SQ names, n_ref of them): a SAM text stream (rsqc_decode_begin_sam), fed with
+        decode_submit_text (plain SAM) or decode_submit (BGZF-compressed SAM); None: a BAM stream."""
         p = abi.DecodeParams()
         p.pipelined = 1 if pipelined else 0
         p.reserve_inflated_bytes = reserve
@@ -168,7 +172,24 @@ class Engine:
             if len(f) == 2:
                 p.filter_tag[k].value = f.encode()
         p.file_index_base = file_index_base
+        if ref_names is not None:
+            if len(ref_names) != n_ref:
+                raise ValueError("ref_names must hold n_ref names")
+            names = (C.c_char_p * max(1, n_ref))(*[n.encode() if isinstance(n, str) else bytes(n) for n in ref_names])
+            self._check(self._l.rsqc_decode_begin_sam(self._h, C.byref(p), names))
+            return
         self._check(self._l.rsqc_decode_begin(self._h, C.byref(p)))
+
+    def decode_submit_text(self, text):
+        """Plain SAM text of a stream begun with ref_names (any cut: a line may straddle calls).  Returns (records, [RefID of
+        every run of records]) as decode_submit."""
+        buf = np.frombuffer(bytes(text), np.uint8) if not isinstance(text, np.ndarray) else text
+        self._keep_decode = buf
+        w = abi.DecodeWindow()
+        self._check(self._l.rsqc_decode_submit_text(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(w)))
+        self._last_window = w
+        runs = list(np.ctypeslib.as_array(C.cast(w.run_tid, C.POINTER(C.c_int32)), (w.n_runs,))) if w.n_runs else []
+        return int(w.n_records), [int(t) for t in runs]
 
     def decode_submit(self, compressed, blocks, skip=0, limit=0):
         """compressed: bytes-like or (address, nbytes); blocks: numpy array of abi BGZF block records (or (address, n)).
