@@ -1,0 +1,266 @@
+// rsqc_ctx.h -- private to csrc/: the context, its buffer types and the helpers that more than one unit of the C ABI calls (rsqc_api.cpp:
+// lifetime, inputs; rsqc_submit.cpp: pools, run_batch; rsqc_finalize.cpp: end of file; rsqc_group.cpp: RCCL; rsqc_decode_api.cpp: BAM / SAM decode)
+#pragma once
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "rsqc_device.h"
+#include "rsqc_decode.h"
+#include "rsqc_sam.h"
+
+// Knobs that make the library SKIP work (wrong or incomplete results) exist only in the diagnostic build (`make prof`,
+// -DRSQC_K1_PROF): the product library does not read them.
+#if defined(RSQC_K1_PROF) || defined(RSQC_DIAG_KNOBS)       /* (`make variant NAME=diag DEFS=-DRSQC_DIAG_KNOBS`: the knobs without the section timers) */
+#define RSQC_DIAG(name) getenv(name)
+// (RSQC_HOST_TRACE=1: host clock at the steps of a pass to stderr -- where a pass spends what the kernels' events do not show)
+namespace rsqc {
+inline void host_trace(const char *what) {
+    static const bool on = getenv("RSQC_HOST_TRACE") != nullptr;
+    if (!on) return;
+    static std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "[host] %-28s +%8.1f us\n", what, std::chrono::duration<double, std::micro>(now - last).count());
+    last = now;
+}
+}  // namespace rsqc
+#define RSQC_TRACE(what) rsqc::host_trace(what)
+#else
+#define RSQC_DIAG(name) ((const char *)nullptr)
+#define RSQC_TRACE(what) ((void)0)
+#endif
+
+namespace rsqc {
+
+struct DevBuf {
+    void *p = nullptr; size_t bytes = 0;
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+struct UploadedBatch {
+    DevBatch d{};
+    std::vector<DevBuf> bufs;
+    uint64_t n = 0, n_cigar_total = 0, file_index_base = 0;
+    std::vector<uint64_t> seg_file_index, seg_records;   // a batch of several file ranges (rsqc_batch.seg_file_index): per segment
+    DevBuf rl_seg;                                   // ... and its per-segment Read-Length inputs [3 * n_seg] (armed at every submit)
+    bool pooled = false;           // transient upload: its buffers go back to the context's pool
+};
+
+// What a submitted batch leaves behind for the end-of-file stage is written into WORST-CASE sized buffers (the counts
+// are only known on the device).  A batch that has completed is RETIRED at the next rsqc_submit / rsqc_wait: its
+// counts are read from a page-locked mirror, what it actually emitted is appended to a growing arena, and the
+// worst-case buffers go back to the pool -- so the memory held until rsqc_finalize is what was emitted (16 B per
+// (gene, name) pair, 28 B per fragment-size candidate, 32 B per GC candidate) plus the buffers of the batches in flight.
+struct PairBuf {                // (gene, qname-hash) pairs of one submitted batch
+    DevBuf rec, counts;         // rec: PairRec[cap] {gene, second name hash (zero for a batch without rsqc_batch.qhash2), name hash}; counts: [n_chunks] per K1 block, then [1] slow-path counter
+    uint64_t cap = 0;           // pair slots allocated
+    uint32_t n_chunks = 0, chunk_cap = 0, slow_base = 0, slow_cap = 0;
+    uint32_t counts_cap = 0;
+    uint64_t pairs_bound = 0;   // most pairs the batch can have emitted
+    uint32_t *h_counts = nullptr;   // page-locked mirror of `counts` (copied when the batch's kernels are done)
+    hipEvent_t done = nullptr;      // the counts have arrived in h_counts
+    hipEvent_t kernels = nullptr;   // the batch's per-record kernels are through (what the copy of the counts waits for, on a side stream)
+    bool used = false;
+};
+struct FragBuf {                // fragment-size candidates of one submitted batch (BED runs only)
+    DevBuf file, qhash, name, endpos, fs, h2, count;
+    DevBuf r_file, r_qhash, r_name, r_endpos, r_fs, r_h2, r_counts;   // the per-record kernel's workgroup regions (packed into the columns above by frag_compact_kernel)
+    uint32_t cap = 0, grid_cap = 0;
+    uint32_t *h_count = nullptr;
+    bool used = false;
+};
+struct GcBuf {                  // fragment GC candidates of one submitted batch (--fasta runs only)
+    DevBuf file, qhash, row, endpos, flag_lq, tid, h2, count;
+    uint32_t cap = 0;
+    uint32_t *h_count = nullptr;
+    bool used = false;
+};
+// growing device arrays of the retired batches: a few parallel columns with one fill level
+struct Arena {
+    DevBuf col[8]; size_t width[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int n_col = 0;
+    uint64_t used = 0, cap = 0;
+};
+
+// device-side BAM decode (rsqc_decode_*): the window buffers are sized once for the largest call and reused; the batch
+// columns a window is parsed into are read by the per-read kernels of that window before the next window's kernels
+// (same stream) overwrite them
+struct DecodeState {
+    bool active = false;
+    BamTagSpec tags{};
+    uint64_t next_file_index = 0, records = 0;
+    uint32_t head = 1u << 22;          // room in front of the window for the carried-over part of a record
+    uint32_t tail = 0;                 // bytes carried over, parked at [head - tail, head)
+    size_t out_cap = 0, comp_cap = 0, blk_cap = 0;
+    DevBuf comp, blocks, ubuf, seg, seg_rec0, seg_ops0, rec_off, ops_at, mark, core, aux, qh2, cigar, seg_tid, seg_start,
+           wide_index, wide_nm, wide_lq, wide_nc, sum, carry, tailtmp, scratch;
+    DecodeSummary *h_sum = nullptr;    // page-locked
+    DevBgzfBlock *h_blocks = nullptr;  // page-locked, blk_cap entries
+    bool unsorted = false;
+    uint64_t n_bad = 0;
+    std::vector<std::string> bad_names;
+    std::vector<const char *> bad_ptrs;
+    // RSQC_DECODE_PROFILE: stage times of the stream, printed at rsqc_decode_end
+    bool profile = false; hipEvent_t pe[4] = {nullptr, nullptr, nullptr, nullptr};
+    double ms_copy = 0, ms_inflate = 0, ms_parse = 0, ms_call = 0; uint64_t prof_in = 0, prof_out = 0, prof_calls = 0;
+    std::chrono::steady_clock::time_point prof_t0;
+    // a call is enqueued, then finished (its summary read, its records submitted) -- at once, or by the next call when the
+    // stream is pipelined: the next call's file bytes then cross PCIe beside this call's kernels
+    bool pipelined = false, pending = false, pend_limited = false;
+    int slot = 0;                      // which half of comp / blocks / h_blocks the call in flight reads
+    DecodeWindow pend_w{};
+    std::chrono::steady_clock::time_point pend_wall0;
+    hipStream_t copy_stream = nullptr; hipEvent_t ev_copy = nullptr;
+    std::vector<int32_t> run_tid;      // contig segments of the last window
+    rsqc_batch last{};                 // the last window's batch (device pointers): rsqc_decode_window::device_batch
+    // a SAM text stream (rsqc_decode_begin_sam): the stages of rsqc_sam.hip instead of the BAM framing and parsing
+    bool sam = false;
+    size_t sam_cap = 0;                // the out_cap the SAM buffers below were sized for
+    uint32_t sam_rec_cap = 0;
+    DevBuf sam_ebits, sam_tbits, sam_segcnt, sam_segk0, sam_rtid, sam_nops, sam_st, sam_sc, sam_scratch, sam_slots, sam_names;
+    SamRefTable sam_refs{};
+    SamStatus *h_sam_st = nullptr;     // page-locked
+    SamWindow pend_s{};
+    uint64_t sam_line0 = 1;            // line number of the first byte of the next window (header lines counted)
+    std::vector<std::string> sam_ref_names;
+    std::vector<int32_t> sam_last_runs;  // rsqc_decode_end: runs of the last window and of the one that ended the last line
+};
+
+}  // namespace rsqc
+using namespace rsqc;            // (every unit that sees this header is host code of the library)
+
+struct rsqc_ctx {
+    rsqc_params params{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string last_error;
+    int sticky = 0;
+    int k1_variant = 41, k1_grid = 256 * 20;  // workgroups of the per-read kernel (RSQC_K1_GRID overrides), set once at create: four rounds of five workgroups per CU
+
+    // annotation (host copies needed at finalize)
+    bool have_ann = false;
+    int32_t n_ref = 0, n_contigs = 0, n_genes = 0, n_listed = 0, n_exons = 0;
+    std::vector<uint32_t> exon_row_id;          // row -> exon id
+    std::vector<DevBuf> ann_bufs;
+    DevAnnotation dann{};
+    DevParams dparams{};
+    // K3 inputs
+    const uint32_t *d_ge_off = nullptr, *d_ge_row = nullptr, *d_gene_cov_off = nullptr, *d_gene_coding = nullptr;
+    const uint8_t *d_gene_flags = nullptr, *d_gene_owned = nullptr;   // owned by ann_bufs
+    const uint32_t *d_gene_order = nullptr;
+    uint32_t k3_large = 0, k3_medium = 0, k3_xlarge = 0, k3_le6144 = 0, k3_le3072 = 0, k3_le2048 = 0, k3_le1024 = 0;
+    int stream_prio = 0, prio_side = 0;         // RSQC_STREAM_PRIO (rsqc_create)
+    uint32_t n_exons_outside_gene = 0;          // of the annotation in use (rsqc_results.exons_outside_gene_row)
+    hipEvent_t fin_e0 = nullptr, fin_e1 = nullptr;
+    uint64_t cov_entries = 0;
+    bool have_bed = false;
+
+    // accumulators
+    // one device arena holds every small result vector (single memset at reset, single D2H at finalize):
+    // u64[3G+K] | u64 bias3,bias5[L] | f64 exon_acc[E] | f64 gmean,gstd,gcv[L] | f64 ecv[E] | u8 gvalid[L] | u8 ecv_valid[E] | u8 exon_hit[E] | misc[64]
+    DevBuf d_arena, d_cov, d_ovf_index, d_tiles;
+    DevBuf d_defer;                             // classify_ei_kernel's deferred list (per-workgroup regions, then the dense list): reused batch after batch (stream order)
+    DevBuf d_ei_rank;                                   // rank table of the interval index
+    char *h_arena = nullptr;                      // pinned host mirror
+    size_t arena_bytes = 0, off_u64 = 0, off_exon = 0, off_gmean = 0, off_gstd = 0, off_gcv = 0, off_bias3 = 0,
+           off_bias5 = 0, off_ecv = 0, off_gvalid = 0, off_ecvv = 0, off_ehit = 0, off_misc = 0;
+    hipStream_t stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;   // K3 (three size classes) runs beside K4
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr, ev_join4 = nullptr;
+    DevAccum acc{};
+    uint64_t tile_cap = 0;
+    std::vector<PairBuf> pair_pool;
+    std::vector<size_t> pairs_in_flight;        // indices into pair_pool, submission order (batches not retired yet)
+    Arena pair_arena, frag_arena, gc_arena;     // what the retired batches emitted
+    DevBuf d_arena_count;                       // u32: pair_arena.used for the K4 launch over the arena
+    std::vector<DevBuf> parked;                 // outgrown arena columns, freed at the next synchronisation point
+    DevBuf d_table, d_tab_off, d_tab_cap;
+    std::vector<FragBuf> frag_pool;
+    std::vector<size_t> frags_in_flight;
+    uint32_t frag_remaining = 0;
+    // --fasta
+    bool have_ref = false;
+    DevBuf d_ref_bits, d_ref_off, d_ref_len, d_gc_bins, d_exon_gc;
+    DevReference dref{};
+    std::vector<GcBuf> gc_pool;
+    std::vector<size_t> gcs_in_flight;
+    std::vector<uint64_t> h_gc;                 // [RSQC_GC_BINS + 1]
+    std::vector<double> h_exon_gc;              // by exon id
+    SortScratch gc_scratch, frag_scratch;
+    uint32_t frag_kept = 0;                     // samples run_fragment_sizes left in frag_scratch (k1 / v1)
+    // K3 outputs
+    bool finalized = false;
+
+    // batches
+    std::vector<UploadedBatch *> resident;
+    std::vector<UploadedBatch *> transient;     // owned by submit(), freed at wait()
+    uint64_t next_record_base = 0;
+    bool have_ranges = false;                   // a batch of several file ranges was submitted in this pass: Read Length is composed on the host
+    bool have_composed_rl = false; int32_t composed_rl = 0;
+    bool early_copied = false;                  // run_finalize_kernels copied everything but geneFragmentCounts and the status words beside the fragment kernels
+    std::vector<uint32_t> h_rl_arm;
+    int name_mode = -1;                         // -1 no batch yet in this pass; 0 batches without qhash2 (64-bit names); 1 with (96-bit names)
+    // per submitted batch: file index of its first record and the Read-Length transfer function the KR kernel leaves
+    // on the device (rsqc_shard_info)
+    std::vector<uint64_t> batch_file_index, batch_records;
+    DevBuf d_rl_summary;
+    uint32_t *h_rl_raw = nullptr;               // page-locked (a copy into pageable memory would hold the host until the coverage kernel ahead of it ended)
+    size_t h_rl_raw_cap = 0;                    // ... words
+    std::vector<uint32_t> h_rl_offset, h_rl_span;
+    std::vector<int32_t> h_rl_state;
+    std::vector<uint64_t> h_sample_file;        // fragment-size samples kept by this shard (first N by file index), ascending
+    std::vector<uint32_t> h_sample_size;
+
+    // timing
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> k1_events, h2d_events, long_events;
+    std::vector<DevBuf> upload_pool;            // device buffers of retired transient uploads
+    std::vector<hipEvent_t> event_pool;
+    rsqc_timing timing{};
+
+    DecodeState dec;
+
+    // host results
+    std::vector<uint64_t> h_fcount;
+    std::vector<int64_t> h_fsize;
+    rsqc_results results{};
+};
+
+#define HIP_TRY(c, expr)                                                                         \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail((c), RSQC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+
+namespace rsqc {
+
+int fail(rsqc_ctx *c, int code, const std::string &msg);
+int dev_alloc(rsqc_ctx *c, DevBuf &b, size_t bytes, bool zero);
+hipEvent_t get_event(rsqc_ctx *c);
+int resolve_events(rsqc_ctx *c);
+// device buffer of at least `bytes` from the context's pool of retired upload buffers (smallest that fits), or empty
+DevBuf take_pooled(rsqc_ctx *c, size_t bytes);
+void free_batch(UploadedBatch *u);
+// a transient batch whose kernels have completed: keep its device buffers for the next rsqc_submit
+void retire_batch(rsqc_ctx *c, UploadedBatch *u);
+// n entries of the columns src[] appended to the arena (grown when it has to be), on stream s
+int arena_append(rsqc_ctx *c, Arena &a, const void *const *src, uint32_t n, hipStream_t s);
+void free_parked(rsqc_ctx *c);                 // caller: the stream has been synchronised
+int retire_completed(rsqc_ctx *c, bool all);
+int run_batch(rsqc_ctx *c, UploadedBatch *u);
+const char *device_error_text(int err);
+
+template <class T>
+int upload(rsqc_ctx *c, std::vector<DevBuf> &owner, const T *host, size_t n, const T **out, bool from_pool = false) {
+    const size_t bytes = n * sizeof(T);
+    // 32 bytes of slack: kernels load a few entries past the end with unconditional, ignored loads
+    DevBuf b = from_pool ? take_pooled(c, bytes + 32) : DevBuf{};
+    if (!b.p) { HIP_TRY(c, hipMalloc(&b.p, bytes + 32)); b.bytes = bytes + 32; }
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+    owner.push_back(b);
+    *out = (const T *)b.p;
+    return 0;
+}
+
+}  // namespace rsqc

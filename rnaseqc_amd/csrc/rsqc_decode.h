@@ -11,6 +11,7 @@
 //   lists    one workgroup: the marks, in record order, become the batch's segment and wide tables
 #pragma once
 
+#include <stddef.h>
 #include "rsqc_bamrec.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -22,6 +23,11 @@ constexpr uint32_t DEC_SEG_BYTES = 8192;
 constexpr uint32_t DEC_MARK_SEG = 1, DEC_MARK_WIDE = 2, DEC_MARK_BADREF = 4, DEC_MARK_JUDGED = 8;
 constexpr uint32_t DEC_ST_INFLATE = 1, DEC_ST_BAD_RECORD = 2;         // DecodeSummary.status bits (inflate: the detail is in inflate_fail)
 constexpr uint32_t DEC_MAX_BAD = 64;
+
+// ---- capacities: what the C ABI allocates (rsqc_decode_api.cpp reserve_columns) for a window buffer of buf_bytes: a record is at
+// least 36 bytes, an operation 4 bytes of its record.  The host emulation of the tests sizes its arrays with the same function.
+struct DecCaps { size_t rec, seg, cigar_bytes; };
+inline DecCaps dec_caps(size_t buf_bytes) { return DecCaps{buf_bytes / 36 + 4, buf_bytes / DEC_SEG_BYTES + 4, buf_bytes + 256}; }
 
 struct DevBgzfBlock { uint64_t in_off; uint32_t in_len, out_len, out_off, crc; };
 

@@ -1002,7 +1002,7 @@ classify_ei_kernel(K1Args A) {
     // the range in PIECES of K1E_PIECE records from an LDS counter.  With one fixed quarter per wave the four waves finished
     // up to 100 us apart (dense and sparse stretches cost differently) and waited for each other at the final barrier:
     // 10.8 % of the kernel (profiles/r3_k1_sections_v2.txt).  A piece is still a contiguous, coordinate-sorted run.
-    // record indices are 32-bit inside the kernel (a batch holds fewer than 2^31 records, rsqc_api.cpp: run_batch): 64-bit
+    // record indices are 32-bit inside the kernel (a batch holds fewer than 2^31 records, rsqc_submit.cpp: run_batch): 64-bit
     // indices cost a register pair, a v_cmp_*_u64 and a v_lshl_add_u64 wherever a lane touches one
     const uint32_t n_rec = (uint32_t)b.n;
     uint32_t wg_beg, wg_end;

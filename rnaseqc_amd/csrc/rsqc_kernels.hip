@@ -271,7 +271,7 @@ namespace rsqc {
 
 // ------------------------------------------------------------------ K4 (rsqc_k4.h) and the retirement of a batch's pairs
 // The pairs of a batch live in per-K1-block chunks (+ one slow-path region), each chunk in file order; the pairs of
-// batches that have been retired (rsqc_api.cpp) sit in one dense arena in file order.
+// batches that have been retired (rsqc_submit.cpp) sit in one dense arena in file order.
 #define RSQC_K4_SLOW_BLOCKS 32
 
 // Retirement of a batch: its chunks, one after the other, appended to the arena.  Workgroup k < n_chunks copies chunk k

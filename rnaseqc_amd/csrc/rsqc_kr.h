@@ -20,7 +20,7 @@ namespace rsqc {
 #define RSQC_RL_MAXP 128
 // A batch of several file ranges (rsqc_batch.seg_file_index, DevAccum::rl_seg): one wave PER SEGMENT, each leaves the function of its
 // own record range [seg_start[s], seg_start[s + 1]) in summary slot s; the context's state is then composed on the host from all
-// the slots in file order (rsqc_api.cpp), not here.
+// the slots in file order (rsqc_finalize.cpp), not here.
 __global__ void __launch_bounds__(64)
 read_length_kernel(DevAnnotation a, DevParams p, DevBatch b, DevAccum acc, uint32_t *summary) {
     const int l = lane_id();

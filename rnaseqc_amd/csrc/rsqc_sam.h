@@ -19,7 +19,7 @@
 
 namespace rsqc {
 
-// ---- capacities: what the C ABI allocates (rsqc_api.cpp decode_reserve) for a window buffer of buf_bytes, and what a window may
+// ---- capacities: what the C ABI allocates (rsqc_decode_api.cpp reserve_columns) for a window buffer of buf_bytes, and what a window may
 // use of it.  The host emulation of the tests sizes its arrays with the same functions.
 struct SamCaps { uint32_t rec_alloc, cigar_alloc; };
 inline SamCaps sam_caps(size_t buf_bytes) {

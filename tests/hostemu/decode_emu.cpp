@@ -115,6 +115,9 @@ int emu_decode_window(const uint8_t *buf, uint32_t start, uint32_t end, const Ba
     uint32_t n = 0, ops = 0;
     for (uint32_t s = 0; s < W.n_seg; ++s) { rec0[s] = n; ops0[s] = ops; n += seg[s].n_rec; ops += seg[s].n_ops; }
     sum.n_rec = n; sum.n_ops = ops; sum.consumed_end = consumed; sum.status = bad ? DEC_ST_BAD_RECORD : 0;
+    // what a framed window needs against what the library allocates for a window buffer of this size (rsqc_decode.h: dec_caps)
+    const DecCaps caps = dec_caps(end > start ? end - start : 0);
+    if (!bad && (n > caps.rec || (size_t)ops * 4 > caps.cigar_bytes || (size_t)W.n_seg + 1 > caps.seg)) return 104;
     std::vector<uint32_t> rec_off(n + 1), ops_at(n + 1); std::vector<uint8_t> mark(n + 1);
     W.rec_off = rec_off.data(); W.ops_at = ops_at.data(); W.mark = mark.data();
     if (!bad) {

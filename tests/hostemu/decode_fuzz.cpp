@@ -4,8 +4,8 @@
 // rsqc_decode.hip run per segment and per record) on windows of DAMAGED inflated data, built with
 // -fsanitize=address,undefined.  A BGZF block's CRC-32 only says that the bytes are the ones the writer compressed; a
 // writer's bug, or a file that is not a BAM behind its header, reaches these functions as it is.  Whatever the bytes:
-// every read stays inside [0, end) of the window, every write inside buffers sized the way rsqc_api.cpp's decode_reserve
-// sizes them, every loop ends, and the parallel chain repair leaves what the plain sequential walk leaves (checked inside
+// every read stays inside [0, end) of the window, every write inside buffers sized by the function the library sizes
+// them by (rsqc_decode.h: dec_caps), every loop ends, and the parallel chain repair leaves what the plain sequential walk leaves (checked inside
 // emu_decode_window).  On the GPU the first three are a dead device, not a wrong answer.
 //
 //   decode_fuzz <cases> <seed>      exit 0 = nothing found; the sanitizers abort the process on a finding
@@ -64,15 +64,15 @@ int main(int argc, char **argv) {
         case 10: g_what = "an aux type damaged"; for (uint32_t k = 0; k < 50; ++k) { const uint32_t p = at(); if (w[p] == 'N' || w[p] == 'C' || w[p] == 'c') { if (p + 2 < w.size()) w[p + 2] = (uint8_t)"ZBHd?"[rnd(5)]; } } break;
         default: g_what = "a slice of another place"; { const uint32_t n = 1 + rnd(3000), from = at(), to = at(); for (uint32_t k = 0; k < n && from + k < w.size() && to + k < w.size(); ++k) w[to + k] = w[from + k]; } break;
         }
-        // exact-size heap buffers: the window's bytes; columns sized like decode_reserve sizes them for a window of this many bytes
+        // exact-size heap buffers: the window's bytes; columns of the capacities the library allocates for a window of this many bytes
         const uint32_t start = rnd(3) ? 0u : std::min<uint32_t>((uint32_t)w.size(), rnd(5000)), end = (uint32_t)w.size();
-        const size_t bytes = end - start, n_rec = bytes / 36 + 4;
+        const size_t bytes = end - start, n_rec = dec_caps(bytes).rec;
         uint8_t *buf = (uint8_t *)malloc(end ? end : 1);
         if (end) memcpy(buf, w.data(), end);
         rsqc_rec_core *core = (rsqc_rec_core *)malloc(n_rec * sizeof(rsqc_rec_core));
         rsqc_rec_aux *aux = (rsqc_rec_aux *)malloc(n_rec * sizeof(rsqc_rec_aux));
         uint32_t *qh2 = (uint32_t *)malloc(n_rec * 4);
-        uint32_t *cigar = (uint32_t *)malloc(bytes + 256);
+        uint32_t *cigar = (uint32_t *)malloc(dec_caps(bytes).cigar_bytes);
         int32_t *seg_tid = (int32_t *)malloc(n_rec * 4); uint64_t *seg_start = (uint64_t *)malloc((n_rec + 1) * 8);
         uint64_t *wide_index = (uint64_t *)malloc(n_rec * 8); int32_t *wide_nm = (int32_t *)malloc(n_rec * 4), *wide_lq = (int32_t *)malloc(n_rec * 4);
         uint32_t *wide_nc = (uint32_t *)malloc(n_rec * 4);

@@ -71,7 +71,7 @@ int k4emu_run(uint64_t seed, int n_genes, int n_chunks, int n_names, int hot_rea
     std::vector<std::set<std::pair<uint64_t, uint32_t>>> names(G);
     for (const Pair &p : stream) { gene_reads[p.g]++; names[p.g].insert({p.key == 0ull ? 0x9e3779b97f4a7c15ull : p.key, p.h2}); }
 
-    // ---- the plan's arrays, sized like rsqc_api.cpp sizes them
+    // ---- the plan's arrays, sized like rsqc_finalize.cpp sizes them
     const uint64_t parts_bound = n_pairs / RSQC_K4_PART_READS + G + 1;
     const uint64_t keys_bound = 2 * n_pairs + (uint64_t)RSQC_K4_SUB_CAP * std::min<uint64_t>(parts_bound, n_pairs / RSQC_K4_PART_READS + 1) + 16ull * G + 16;
     const uint32_t lay_blocks = (G + 1023u) / 1024u;
