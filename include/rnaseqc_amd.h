@@ -436,6 +436,16 @@ RSQC_API int rsqc_finalize(rsqc_ctx *ctx, rsqc_results *out);
 /* Zeroes every accumulator (keeps annotation/BED and uploaded batches).       */
 RSQC_API int rsqc_reset(rsqc_ctx *ctx);
 
+/* Replaces a context's inputs (additive to ABI 5): waits for everything in flight, then returns the context to its state
+ * after rsqc_create -- rsqc_set_annotation, rsqc_set_bed and rsqc_set_reference are legal again, for an annotation with other
+ * contigs, genes and exons.  Released: the annotation, BED and reference tables, the accumulators and their host mirror, the
+ * coverage array, the interval index's rank table, whatever the open pass had emitted (a pass that was not finalized is
+ * dropped, an open rsqc_decode_* stream with it) and the sticky error.  Kept: the streams, the event pools, the per-batch
+ * buffer pools, the decode window buffers, the timing sums and the resident batches (rsqc_upload) -- whose contig ids then
+ * have to mean something in the next annotation.  The vectors of an earlier rsqc_results are invalid afterwards.  Not for a
+ * context that is a member of a live rsqc_group.                                                                        */
+RSQC_API int rsqc_clear_inputs(rsqc_ctx *ctx);
+
 RSQC_API int rsqc_get_timing(rsqc_ctx *ctx, rsqc_timing *out);
 RSQC_API int rsqc_reset_timing(rsqc_ctx *ctx);
 

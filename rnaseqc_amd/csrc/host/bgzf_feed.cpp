@@ -55,6 +55,16 @@ BgzfFeeder::~BgzfFeeder() {
 }
 
 bool BgzfFeeder::open(const std::string &path) {
+    // the next file on the same feeder (a cohort): the read-ahead thread of the file before is stopped and joined before any of
+    // its state is reset; the chunk buffers -- page-locked once -- and the CPU share's pool stay
+    if (th_.joinable()) {
+        { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
+        cv_.notify_all();
+        th_.join();
+    }
+    if (fd_ >= 0) { close(fd_); fd_ = -1; }
+    file_size_ = 0; done_ = false;
+    head_ = tail_ = count_ = 0; lent_ = nullptr; eof_ = false; stop_ = false; error_.clear();
     fd_ = ::open(path.c_str(), O_RDONLY);
     if (fd_ < 0) return false;
     struct stat st;

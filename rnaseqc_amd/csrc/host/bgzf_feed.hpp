@@ -30,6 +30,7 @@ public:
     BgzfFeeder(const BgzfFeeder &) = delete;
     BgzfFeeder &operator=(const BgzfFeeder &) = delete;
 
+    // may be called again for the next file: the chunk buffers that reserve() / the first file page-locked are kept
     bool open(const std::string &path);
     // Virtual offset (coffset << 16 | uoffset) of the first alignment record: inflates the header's blocks on the host.
     // names (may be null): the reference sequence names of the header.  Throws std::runtime_error on a file that is not a BAM.

@@ -1,4 +1,4 @@
-// main.cpp -- `rnaseqc [OPTIONS] gtf bam output`: the reference's command line (flag table
+// main.cpp -- `rnaseqc [OPTIONS] gtf bam output` (or `--bam-list=FILE gtf output`, a cohort): the reference's command line (flag table
 // src/RNASeQC.cpp:39-65, defaults :87-100, exit codes :678-766) in front of the HIP hot path.
 // Host side only: GTF/BED ingest, BAM decode into SoA batches, report writers.  Every per-record
 // computation happens on the GPU through the C ABI (include/rnaseqc_amd.h); without a GPU the
@@ -16,6 +16,7 @@
 #include <cstring>
 #include <fstream>
 #include <future>
+#include <map>
 #include <iostream>
 #include <stdexcept>
 #include <string>
@@ -50,6 +51,7 @@ struct Options {
     long bias_offset = 0, bias_window = 100; unsigned long bias_gene_length = 200, coverage_mask = 500, detection = 5;
     std::vector<std::string> tags;
     int gpus = 0;                      // --gpus (extension): GPUs to shard the BAM over by contig; 0 = RSQC_GPUS or 1
+    std::string bam_list; bool has_bam_list = false;   // --bam-list (extension): a cohort, the positionals are `gtf output`
 };
 
 void usage(std::ostream &o) {
@@ -80,7 +82,8 @@ void usage(std::ostream &o) {
          "      --coverage                        Write per-transcript coverage statistics to a table\n"
          "      --coverage-mask=[SIZE]            Bases masked at both transcript ends. Default: 500bp\n"
          "      -d[threshold], --detection-threshold=[threshold]  Counts to call a gene detected. Default: 5 reads\n"
-         "      --gpus=[N]                        (extension) Shard the BAM by contig over N GPUs of this node; needs [bam].bai. Default: 1\n";
+         "      --gpus=[N]                        (extension) Shard the BAM by contig over N GPUs of this node; needs [bam].bai. Default: 1\n"
+         "      --bam-list=[FILE]                 (extension) A cohort on one GPU: FILE lists one input per line, path[<TAB>sample]; the positionals are [gtf] [output]\n";
 }
 
 long to_long(const std::string &flag, const std::string &v) {
@@ -158,6 +161,7 @@ Options parse(int argc, char **argv) {
         else if (name == "rpkm") o.rpkm = true;
         else if (name == "coverage") o.coverage = true;
         else if (name == "gpus") o.gpus = (int)to_ulong(name, need());
+        else if (name == "bam-list") { o.bam_list = need(); o.has_bam_list = true; }
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
         else if (name == "detection-threshold") o.detection = to_ulong(name, need());
         else throw ParseError("Flag could not be matched: " + name);
@@ -204,9 +208,8 @@ constexpr int kFileIndexShift = 36;      // virtual file index of a batch: (cont
 // ---- device decode (rsqc_decode_*): the default.  RSQC_DECODE=host keeps inflate + record parsing on the CPU threads.
 // The device path reads the file with pread through the block feeder, which needs a regular file: a FIFO, /dev/stdin or a
 // process substitution is streamed by the host reader instead (as every input was before the device decode existed).
-bool g_input_is_stream = false;
-bool device_decode_wanted() {
-    if (g_input_is_stream) return false;
+bool device_decode_wanted(bool input_is_stream) {
+    if (input_is_stream) return false;
     const char *e = getenv("RSQC_DECODE");
     return !(e && (!strcmp(e, "host") || !strcmp(e, "cpu")));
 }
@@ -363,25 +366,771 @@ int merge_shards(std::vector<Shard> &shards, uint32_t fragment_samples, ShardMer
     return RSQC_OK;
 }
 
+namespace {
+
+using Clock = std::chrono::steady_clock;
+double seconds_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+const char *const kUnsortedWarning = "Warning: The input bam does not appear to be sorted. An unsorted bam will yield incorrect results";
+
+// The exception in flight as the reference's exit code, its message on stderr behind `prefix` (src/RNASeQC.cpp:678-766; the
+// argument errors that print the usage text are main()'s own).  Called from a catch (...) block.
+int explain_exception(const std::string &prefix) {
+    using std::cerr; using std::endl;
+    try { throw; }
+    catch (std::invalid_argument &e) { cerr << prefix << "Invalid argument type provided: " << e.what() << endl; return 7; }
+    catch (FileError &e) { cerr << prefix << e.what() << endl; return 10; }
+    catch (GtfError &e) { cerr << prefix << "Failed to parse the GTF: " << e.what() << endl; return 11; }
+    catch (BedError &e) { cerr << prefix << "Failed to parse the BED: " << e.what() << endl; return 11; }
+    catch (std::length_error &e) { cerr << prefix << "Unable to parse the GFT lines" << endl << e.what() << endl; return 1; }
+    catch (std::range_error &e) { cerr << prefix << "Invalid range" << endl << e.what() << endl; return 2; }
+    catch (std::domain_error &e) { cerr << prefix << "Unable to perform string conversion" << endl << e.what() << endl; return 3; }
+    catch (std::bad_alloc &e) { cerr << prefix << "Memory allocation failure. Out of memory" << endl << e.what() << endl; return 10; }
+    catch (std::exception &e) { cerr << prefix << "Encountered an IO failure" << endl << e.what() << endl; return 10; }
+    catch (...) { cerr << prefix << "Unknown error" << endl; return -1; }
+}
+
+// ---- one input, opened: its format by content and its header.  Nothing here touches the GPU, so a cohort does this for
+// sample k+1 on a thread beside sample k's decode.
+struct Input {
+    std::string path;
+    bool is_stream = false;                           // a FIFO / stdin: streamed by the host (the block feeder needs pread)
+    InputFormat fmt = InputFormat::Unknown;
+    std::vector<std::string> contigs;                 // the header's reference names, in order
+    uint64_t first_voff = 0, file_size = 0;           // BAM for the device decode: virtual offset of the first record
+    std::unique_ptr<SamTextFeeder> stream_feed;       // SAM text from a stream: holds the bytes that were read to sniff it
+    std::unique_ptr<BamReader> reader;                // BAM decoded on the host (RSQC_DECODE=host, or a stream)
+    std::string error;                                // not empty: the input cannot be opened (exit code 10)
+    Clock::time_point t_open;
+    bool sam() const { return fmt == InputFormat::SamText || fmt == InputFormat::SamBgzf; }
+};
+
+std::unique_ptr<Input> open_input(const std::string &path, const Options &o) {
+    std::unique_ptr<Input> in(new Input());
+    in->path = path; in->t_open = Clock::now();
+    const std::string unable = "Unable to open BAM file: " + path;
+    { struct stat st; if (stat(path.c_str(), &st) == 0) { in->is_stream = !S_ISREG(st.st_mode); in->file_size = (uint64_t)st.st_size; } }
+    // the input's format by its content
+    in->fmt = in->is_stream ? InputFormat::Unknown : sniff_file(path);
+    std::string reader_path = path;                   // what the host BAM reader opens
+    if (in->is_stream) {
+        // a FIFO / stdin: its first bytes are read to tell the format and stay the first chunk's; a BAM is handed on to the
+        // host reader through a pipe of this process that replays them
+        in->stream_feed.reset(new SamTextFeeder());
+        if (!in->stream_feed->open(path)) { in->error = unable; return in; }
+        const std::vector<uint8_t> &first = in->stream_feed->peek(1 << 16);
+        in->fmt = sniff_format(first.data(), first.size());
+        if (in->fmt == InputFormat::Bam || in->fmt == InputFormat::Unknown) {
+            int pfd[2];
+            if (pipe(pfd) != 0) { in->error = unable; return in; }
+            signal(SIGPIPE, SIG_IGN);
+            const int src = in->stream_feed->release_fd();
+            std::thread([src, pfd, head = in->stream_feed->peek(0)]() {
+                auto put = [&](const uint8_t *b, size_t n) { while (n) { const ssize_t w = write(pfd[1], b, n); if (w <= 0) return false; b += w; n -= (size_t)w; } return true; };
+                bool ok = put(head.data(), head.size());
+                std::vector<uint8_t> buf(1 << 20);
+                while (ok) { const ssize_t g = read(src, buf.data(), buf.size()); if (g <= 0) break; ok = put(buf.data(), (size_t)g); }
+                close(pfd[1]); close(src);
+            }).detach();
+            reader_path = "/dev/fd/" + std::to_string(pfd[0]);
+            in->stream_feed.reset();
+            in->fmt = InputFormat::Bam;
+        }
+    }
+    if (in->fmt == InputFormat::PlainGzip) { in->error = unable + " (gzip-compressed but not BGZF: recompress it with bgzip)"; return in; }
+    if (in->fmt == InputFormat::SamBgzf && in->is_stream) {
+        in->error = unable + " (BGZF-compressed SAM is read from a regular file only: decompress it into the pipe)"; return in;
+    }
+    // The header.  SAM (plain or BGZF-compressed): the @SQ lines are read here, the text goes to the device SAM stages.  BAM with
+    // the device decode (the default): the host only inflates the header's own blocks; the multi-threaded CPU reader (whose
+    // pools start inflating the file as soon as it is opened) comes up only for RSQC_DECODE=host and for streams.
+    if (in->sam()) {
+        SamHeader hdr;
+        if (in->stream_feed) {
+            bool complete = false;
+            for (size_t want = 1 << 16;; want *= 2) {
+                const auto &hd = in->stream_feed->peek(want);
+                hdr = SamHeader{};
+                parse_sam_header((const char *)hd.data(), hd.size(), hdr, complete);
+                if (complete || hd.size() < want) break;
+            }
+        } else if (!read_sam_header(path, hdr)) { in->error = unable; return in; }
+        in->contigs = hdr.names;
+    } else if (device_decode_wanted(in->is_stream)) {
+        BgzfFeeder probe;
+        if (!probe.open(path)) { in->error = unable; return in; }
+        try { in->first_voff = probe.first_record_voffset(&in->contigs); }
+        catch (std::exception &) { in->error = unable; return in; }
+    } else {
+        in->reader.reset(new BamReader());
+        if (!in->reader->open(reader_path)) { in->error = unable; in->reader.reset(); return in; }
+        in->reader->set_tags(o.chimeric_tag, o.tags);
+        in->contigs = in->reader->contigs();
+    }
+    return in;
+}
+
+// ---- what a process sets up once and every sample of it uses: the context, its inputs, the page-locked buffers
+struct Session {
+    rsqc_params P{};
+    rsqc_ctx *gpu = nullptr;
+    std::future<int> gpu_ready;                        // rsqc_create, beside the GTF parse
+    int gpu_rc = RSQC_OK; bool gpu_asked = false;
+    Clock::time_point t_start, t_gtf0, t_gtf1, t_gpu0, t_gpu1, t_loop0, t_loop1, t_rep0, t_rep1;
+    // the annotation as parsed: chromosomeMap before any input's header joined it, and the chromosomes with GTF features
+    std::map<std::string, int> base_chrom_id; std::vector<std::string> base_chrom_name;
+    std::vector<char> gtf_chrom;
+    // the header the annotation is flattened for, and what of it the context holds
+    bool flattened = false, inputs_set = false, needs_reset = false;
+    bool dirty = false;                                // a pass that did not reach its results is in the context
+    std::vector<std::string> contigs;
+    FastaFile fasta;
+    std::vector<std::vector<uint8_t>> fasta_seq;
+    bool keep_fasta = false;                           // a cohort: the bases stay on the host for the next set of inputs
+    std::vector<char> in_fasta;
+    std::future<void> fasta_loaded;                    // (declared behind what its thread fills: its destructor joins the reader first)
+    // feeders and staging, page-locked once
+    std::unique_ptr<BgzfFeeder> feed; std::string feed_path; bool feed_ready_checked = true, feed_prepared = false;
+    std::future<bool> feed_ready;                      // the feeder's buffers, page-locked beside the GTF parse
+    std::unique_ptr<SamTextFeeder> sam_feed;
+    std::unique_ptr<HostBatch[]> bufs;
+    bool decode_reserved = false; uint64_t reserve_file_size = 0;
+    // a cohort: messages carry the sample's name, the reports are written on a thread beside the next sample (one job at most)
+    std::string prefix;
+    bool async_reports = false;
+    std::future<void> report_job;
+    void finish_reports() { if (report_job.valid()) report_job.get(); }
+};
+
+int feeder_cpu_threads() {
+    const int spare = effective_cpus() - 4;
+    return getenv("RSQC_DECODE_CPU_THREADS") ? atoi(getenv("RSQC_DECODE_CPU_THREADS")) : (spare >= 4 ? spare : 0);
+}
+size_t feeder_chunk_bytes() { return getenv("RSQC_DECODE_CHUNK") ? (size_t)atoll(getenv("RSQC_DECODE_CHUNK")) : (size_t)512 << 20; }
+uint64_t feeder_max_out_bytes() { return getenv("RSQC_DECODE_MAX_OUT") ? (uint64_t)atoll(getenv("RSQC_DECODE_MAX_OUT")) : (uint64_t)1024 << 20; }
+bool feeder_prepin() { return !(getenv("RSQC_FEED_PREPIN") && !atoi(getenv("RSQC_FEED_PREPIN"))); }
+
+// The page-locked chunk buffers of the device decode's feeder (one GPU: ~1.3 GB, a few hundred ms of page-locking) come up
+// beside the GTF parse.  `path`: the file whose size and compression the buffers are sized for -- a cohort's largest BAM.  A
+// file that cannot be opened is reported later, where the reference reports it.
+void start_early_feeder(Session &S, const std::string &path) {
+    S.feed.reset(new BgzfFeeder());
+    S.feed_path = path;
+    BgzfFeeder *ef = S.feed.get();
+    const int ct = feeder_cpu_threads();
+    const size_t chunk = feeder_chunk_bytes();
+    const uint64_t max_out = feeder_max_out_bytes();
+    S.feed_ready_checked = false;
+    S.feed_ready = std::async(std::launch::async, [ef, path, ct, chunk, max_out] {
+        try {
+            if (!ef->open(path)) return false;
+            // (the room behind a chunk's file bytes is page-locked for the largest share the CPUs can reach: 12 threads have
+            //  settled at 0.10-0.25 of a call on every file measured; 0.5 only where there are the threads for it)
+            if (ct > 0) ef->set_cpu_share(ct, 0.15, std::min(0.5, std::max(0.1, 0.025 * ct)), max_out);
+            ef->reserve(chunk, max_out);
+            return true;
+        } catch (std::exception &) { return false; }
+    });
+}
+
+// annotation and BED of one context; 0, or the exit code with the message printed
+int set_annotation_and_bed(const Options &o, Annotation &ann, rsqc_ctx *gpu, const uint8_t *owned, bool warn, const std::string &prefix, int &rc) {
+    using std::cerr; using std::endl;
+    if ((rc = rsqc_set_annotation(gpu, &ann.ann, owned)) != RSQC_OK) {
+        // (the GTF parsed: this is the device index refusing the annotation -- e.g. no memory for the interval tables -- and
+        //  its own message says which)
+        cerr << prefix << "Unable to build the annotation index on the GPU: " << rsqc_last_error(gpu) << endl; return 11;
+    }
+    // accepted with a warning (an exon outside its gene's row): the reference's counterpart is its per-read
+    // "Gene encountered after computing coverage" (src/Metrics.cpp:108-112); said once, before the BAM loop
+    if (warn && rsqc_last_error(gpu)[0]) cerr << prefix << "Warning: " << rsqc_last_error(gpu) << endl;
+    if (o.has_bed && (rc = rsqc_set_bed(gpu, &ann.bed)) != RSQC_OK) { cerr << prefix << "Failed to parse the BED: " << rsqc_last_error(gpu) << endl; return 11; }
+    return 0;
+}
+// --fasta: the contigs of the FASTA index that the flattened annotation names, on every context
+int set_reference(Session &S, Annotation &ann, const std::vector<rsqc_ctx *> &ctxs, int &rc) {
+    using std::cerr; using std::endl;
+    if (S.fasta_loaded.valid()) S.fasta_loaded.get();                     // FileError -> 10
+    S.in_fasta.assign(ann.contig_names.size(), 0);
+    std::vector<int32_t> r_contig; std::vector<uint64_t> r_len; std::vector<const uint8_t *> r_seq;
+    for (size_t i = 0; i < S.fasta.index.size(); ++i) {
+        int cid = -1;
+        for (size_t k = 0; k < ann.contig_names.size(); ++k) if (ann.contig_names[k] == S.fasta.index[i].name) { cid = (int)k; break; }
+        if (cid < 0) continue;                                            // a contig neither the BAM nor the GTF/BED names
+        r_contig.push_back(cid); r_len.push_back(S.fasta_seq[i].size()); r_seq.push_back(S.fasta_seq[i].data());
+        S.in_fasta[(size_t)cid] = 1;
+    }
+    rsqc_reference ref{(int32_t)r_contig.size(), r_contig.data(), r_len.data(), r_seq.data()};
+    for (rsqc_ctx *gpu : ctxs)
+        if ((rc = rsqc_set_reference(gpu, &ref)) != RSQC_OK) { cerr << S.prefix << "Failed to load the reference: " << rsqc_last_error(gpu) << endl; return 10; }
+    if (!S.keep_fasta) std::vector<std::vector<uint8_t>>().swap(S.fasta_seq);   // the bases live on the device now
+    return 0;
+}
+
+// header check: at least one BAM contig must carry GTF features (src/RNASeQC.cpp:216-238)
+bool shares_contigs(const Session &S, const Annotation &ann, const std::vector<std::string> &contigs) {
+    for (auto &n : contigs) {
+        auto it = ann.chrom_id.find(n);
+        if (it != ann.chrom_id.end() && (size_t)it->second < S.gtf_chrom.size() && S.gtf_chrom[(size_t)it->second]) return true;
+    }
+    return false;
+}
+// the annotation flattened against a header's contig order (the BED and the reference follow: their contig ids come from the same map)
+void flatten_for(Session &S, Annotation &ann, const std::vector<std::string> &contigs) {
+    S.finish_reports();                                    // (the writer of the sample before reads the flattened tables)
+    if (S.flattened) { ann.chrom_id = S.base_chrom_id; ann.chrom_name = S.base_chrom_name; }   // as a run of this input alone sees chromosomeMap
+    ann.flatten(contigs);
+    S.contigs = contigs; S.flattened = true;
+}
+
+// what the report writer reads of rsqc_results, in memory of its own: the vectors behind rsqc_results are the context's and
+// valid only until its next rsqc_finalize
+struct ResultsCopy {
+    rsqc_results res{};
+    std::vector<std::vector<char>> store;
+    template <class T> void keep(const T *&p, size_t n) {
+        if (!p) return;
+        store.emplace_back(std::max<size_t>(n, 1) * sizeof(T));
+        memcpy(store.back().data(), p, n * sizeof(T));
+        p = (const T *)store.back().data();
+    }
+    explicit ResultsCopy(const rsqc_results &r) : res(r) {
+        const size_t L = (size_t)std::max(r.n_genes_listed, 0), E = (size_t)std::max(r.n_exons, 0);
+        keep(res.gene_reads, L); keep(res.gene_unique, L); keep(res.gene_fragments, L);
+        keep(res.exon_reads, E); keep(res.exon_hit, E);
+        keep(res.gene_cov_mean, L); keep(res.gene_cov_std, L); keep(res.gene_cov_cv, L); keep(res.gene_cov_valid, L);
+        keep(res.exon_cv, E); keep(res.exon_cv_valid, E);
+        keep(res.bias_three, L); keep(res.bias_five, L);
+        keep(res.fragment_size, r.n_fragment_sizes); keep(res.fragment_count, r.n_fragment_sizes);
+        keep(res.gc_bins, RSQC_GC_BINS); keep(res.exon_gc, E);
+    }
+};
+
+struct Sample { std::string path, name; bool name_given = false; std::future<std::unique_ptr<Input>> opened; };   // name_given: as --sample (the GCT value column)
+// a row of cohort.tsv
+struct SampleRow { std::string sample, input, format = "not run"; uint64_t records = 0; double seconds = 0; int exit_code = 0; bool fatal = false; };
+
+// ---- one sample on one GPU: the input opened and its header read (or taken over from the thread that did), the contig check,
+// the context's inputs (set, kept, or replaced when the header's contigs differ from the sample before), the decode loop,
+// finalize and the reports.  Returns the exit code of a run of this input alone; throws what main() maps to exit codes.
+int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, const std::string &out_dir, SampleRow &row) {
+    using std::cerr; using std::cout; using std::endl;
+    std::unique_ptr<Input> opened = sample.opened.valid() ? sample.opened.get() : open_input(sample.path, o);
+    Input &in = *opened;
+    const std::string &path = in.path;
+    const Clock::time_point t_open = in.t_open;
+    struct Timer { SampleRow &row; Clock::time_point t0; bool armed = true; ~Timer() { if (armed) row.seconds = seconds_between(t0, Clock::now()); } } timer{row, t_open};
+    row.format = input_format_name(in.fmt);
+    if (!in.error.empty()) { cerr << S.prefix << in.error << endl; return 10; }
+    const bool sam_input = in.sam();
+    const std::vector<std::string> &bam_contigs = in.contigs;
+    if (sam_input && o.verbosity > 1) cout << "Input: " << input_format_name(in.fmt) << " (" << bam_contigs.size() << " @SQ lines), parsed on the GPU" << endl;
+    if (o.verbosity > 1) cout << "Checking bam header..." << endl;
+    if (!shares_contigs(S, ann, bam_contigs)) { cerr << S.prefix << "BAM file shares no contigs with GTF" << endl; return 11; }
+    const bool same_header = S.flattened && bam_contigs == S.contigs;
+    if (!same_header) flatten_for(S, ann, bam_contigs);
+    const int n_ref_bam = (int)bam_contigs.size();
+
+    // ---- the context and its inputs
+    if (!S.gpu_asked) {
+        S.t_gpu0 = Clock::now();
+        S.gpu_rc = S.gpu_ready.get();
+        S.t_gpu1 = Clock::now();
+        S.gpu_asked = true;
+    }
+    if (S.gpu_rc != RSQC_OK) { cerr << S.prefix << "Unable to initialise the GPU hot path: " << rsqc_strerror(S.gpu_rc) << endl; row.fatal = true; return 10; }
+    rsqc_ctx *gpu = S.gpu;
+    int rc;
+    auto hip_failed = [&](int code) { if (code == RSQC_ERR_HIP) row.fatal = true; return code; };
+    if (S.dirty || (S.inputs_set && !same_header)) {
+        // another contig order, or a sample that failed in the middle of its pass: everything in flight is waited for and the
+        // context is as rsqc_create left it (its streams, pools and decode buffers kept)
+        if ((rc = rsqc_clear_inputs(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+        S.inputs_set = false; S.dirty = false; S.needs_reset = false;
+    }
+    if (!S.inputs_set) {
+        S.dirty = true;                                                    // (a set that fails half-way is cleared before the next one)
+        if (int code = set_annotation_and_bed(o, ann, gpu, nullptr, true, S.prefix, rc)) { hip_failed(rc); return code; }
+        if (o.has_fasta) if (int code = set_reference(S, ann, {gpu}, rc)) { hip_failed(rc); return code; }
+        S.inputs_set = true; S.dirty = false;
+    } else if (S.needs_reset) {
+        if ((rc = rsqc_reset(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    }
+    S.needs_reset = false;
+
+    const bool device_decode = device_decode_wanted(in.is_stream) && !sam_input;
+    if (device_decode && !S.decode_reserved && !(getenv("RSQC_DECODE_PRERESERVE") && !atoi(getenv("RSQC_DECODE_PRERESERVE")))) {
+        // the device's window buffers are set up before the loop, like the host path's page-locked batches below: once, for the
+        // largest file the process will read
+        rsqc_decode_params dp = decode_params(o, n_ref_bam, 0);
+        dp.reserve_inflated_bytes = decode_reserve_bytes(std::max(S.reserve_file_size, in.file_size));
+        rsqc_decode_info none{};
+        if ((rc = rsqc_decode_begin(gpu, &dp)) != RSQC_OK || (rc = rsqc_decode_end(gpu, &none)) != RSQC_OK) {
+            cerr << S.prefix << "Unable to set up the device decode: " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10;
+        }
+        S.decode_reserved = true;
+    }
+    // the feeder's chunk buffers are page-locked here, before the loop: page-locking takes the HIP runtime's lock, and done
+    // by the read-ahead thread during the loop it stalled the thread that feeds the GPU (193 -> 237 M reads/s)
+    if (device_decode) {
+        // RSQC_DECODE_CPU_THREADS=n: n spare CPU threads inflate the tail of every chunk beside the GPU (BgzfFeeder::set_cpu_share)
+        // (default: the CPUs the process may use minus four for the file reads and the thread that feeds the GPU; measured on the
+        //  16-CPU box, 12 threads: 258 -> 279 M reads/s, 85 -> 97 M on the realistic-entropy file, profiles/r2_decode_cpu_share_ab.txt)
+        if (!S.feed_ready_checked) {
+            S.feed_ready_checked = true;
+            if (S.feed_ready.get()) S.feed_prepared = true; else S.feed.reset();
+        }
+        if (!S.feed) { S.feed.reset(new BgzfFeeder()); S.feed_path.clear(); S.feed_prepared = false; }
+        if (S.feed_path != path) {                     // (the next file of a cohort: the buffers stay)
+            S.feed_path.clear();
+            if (!S.feed->open(path)) { cerr << S.prefix << "Unable to open BAM file: " << path << endl; return 10; }
+            S.feed_path = path;
+        }
+        if (!S.feed_prepared) {
+            const int cpu_share_threads = feeder_cpu_threads();
+            if (cpu_share_threads > 0) S.feed->set_cpu_share(std::max(1, cpu_share_threads), 0.15, 0.5, (uint64_t)1 << 30);
+            if (feeder_prepin()) S.feed->reserve(feeder_chunk_bytes());
+            S.feed_prepared = true;
+        }
+        // (threads that read one chunk's slices side by side; RSQC_FEED_READ_THREADS overrides)
+        S.feed->read_threads = getenv("RSQC_FEED_READ_THREADS") ? std::max(1, atoi(getenv("RSQC_FEED_READ_THREADS"))) : std::max(1, std::min(8, effective_cpus() / 2));
+    }
+    if (o.verbosity) cout << "Parsing bam..." << endl;
+    std::vector<int> visit;
+    unsigned long long alignmentCount = 0;
+    bool warned_unsorted = false;
+    auto warn_unsorted = [&] { if (!warned_unsorted) { cerr << S.prefix << kUnsortedWarning << endl; warned_unsorted = true; } };
+    // a contig the input visits: the order of coverage.tsv, the sort check, the FASTA's gaps (src/RNASeQC.cpp:350-355)
+    auto visit_contig = [&](int32_t t, bool &revisit) {
+        if (t < 0 || (!visit.empty() && visit.back() == t)) return;
+        if (std::find(visit.begin(), visit.end(), t) != visit.end()) revisit = true;     // a contig that comes back
+        visit.push_back(t);
+        if (o.has_fasta && (size_t)t < S.in_fasta.size() && !S.in_fasta[(size_t)t])
+            cerr << S.prefix << "Warning: Provided Fasta does not contain chromosome " << ann.contig_names[(size_t)t]
+                 << ". No GC statistics will be collected for this chromosome" << endl;
+    };
+    auto on_window = [&](const rsqc_decode_window &w) {
+        bool revisit = false;
+        for (uint32_t k = 0; k < w.n_runs; ++k) visit_contig(w.run_tid[k], revisit);
+        if (revisit) warn_unsorted();
+        alignmentCount += w.n_records;
+        row.records = alignmentCount;
+        if (o.verbosity > 1) cout << "Alignments processed: " << alignmentCount << endl;
+    };
+    // stderr of the reference's loop: the names of records with a RefID the header lacks (src/RNASeQC.cpp:333-337, under -v)
+    // and the sort warning (:354-355).  The reference repeats the warning for every offending record; it is given
+    // once here -- an unsorted file voids the results either way (the static index does not reproduce what the
+    // reference's destructively trimmed window would count).
+    auto after_stream = [&](int code, const rsqc_decode_info &di) {
+        if (code == RSQC_ERR_INPUT) throw std::runtime_error(rsqc_last_error(gpu));
+        if (code != RSQC_OK) return;
+        if (o.verbosity) for (int k = 0; k < di.n_bad_refid && k < 64; ++k) cerr << S.prefix << "Unrecognized RefID on alignment: " << di.bad_refid[k] << endl;
+        if (di.unsorted) warn_unsorted();
+    };
+    S.dirty = true;
+    S.t_loop0 = Clock::now();
+    rc = RSQC_OK;
+    if (sam_input) {
+        // ---- SAM text: the host reads the file (plain) or frames its BGZF blocks, the device does the rest
+        rsqc_decode_info di{};
+        std::vector<const char *> names;
+        for (auto &nm : bam_contigs) names.push_back(nm.c_str());
+        if (in.fmt == InputFormat::SamBgzf) {
+            BgzfFeeder feed;
+            if (!feed.open(path)) { cerr << S.prefix << "Unable to open BAM file: " << path << endl; return 10; }
+            feed.read_threads = std::max(1, std::min(8, effective_cpus() / 2));
+            rc = decode_range(gpu, feed, decode_params(o, n_ref_bam, 0), 0, 0, di, on_window, names.data());
+        } else {
+            SamTextFeeder *sam_feed = in.stream_feed.get();
+            if (!sam_feed) {                           // a regular file: the process's feeder, its chunk buffers page-locked once
+                if (!S.sam_feed) S.sam_feed.reset(new SamTextFeeder());
+                if (!S.sam_feed->open(path)) { cerr << S.prefix << "Unable to open BAM file: " << path << endl; return 10; }
+                sam_feed = S.sam_feed.get();
+            }
+            // (RSQC_SAM_CHUNK: bytes of text per call; the tests use small values so that lines straddle many calls)
+            const size_t chunk = getenv("RSQC_SAM_CHUNK") ? (size_t)atoll(getenv("RSQC_SAM_CHUNK")) : (size_t)256 << 20;
+            rsqc_decode_params dp = decode_params(o, n_ref_bam, 0);
+            dp.pipelined = 1;
+            dp.reserve_inflated_bytes = chunk + (1u << 20);
+            rc = rsqc_decode_begin_sam(gpu, &dp, names.data());
+            if (rc == RSQC_OK) {
+                sam_feed->start(chunk);
+                while (SamTextFeeder::Chunk *ch = sam_feed->next()) {
+                    rsqc_decode_window w{};
+                    rc = rsqc_decode_submit_text(gpu, ch->data, ch->bytes, &w);
+                    if (rc != RSQC_OK) break;
+                    if (w.n_records) on_window(w);
+                }
+                if (rc != RSQC_OK) { rsqc_decode_info dropped{}; (void)rsqc_decode_end(gpu, &dropped); }
+                else {
+                    if (!sam_feed->error().empty()) { rsqc_decode_info dropped{}; (void)rsqc_decode_end(gpu, &dropped); throw std::runtime_error(sam_feed->error()); }
+                    rc = rsqc_decode_end(gpu, &di);
+                    if (rc == RSQC_OK && di.last.n_records) on_window(di.last);
+                }
+            }
+        }
+        after_stream(rc, di);
+    } else if (device_decode) {
+        // ---- device decode: the host reads the file and frames the BGZF blocks, nothing else
+        rsqc_decode_info di{};
+        rc = decode_range(gpu, *S.feed, decode_params(o, n_ref_bam, 0), in.first_voff, 0, di, on_window);
+        after_stream(rc, di);
+    } else {
+        // ---- host decode: inflate and record parsing on the CPU threads, batches through page-locked staging sized once
+        const size_t BATCH = getenv("RSQC_BATCH") ? (size_t)atol(getenv("RSQC_BATCH")) : (size_t)1 << 21;
+        if (!S.bufs) {
+            S.bufs.reset(new HostBatch[2]);
+            for (int k = 0; k < 2; ++k) {
+                HostBatch &hb = S.bufs[k];
+                hb.core.use_pinned(true); hb.aux.use_pinned(true); hb.qh2.use_pinned(true); hb.cigar.use_pinned(true);
+                hb.core.reserve(BATCH); hb.aux.reserve(BATCH); hb.qh2.reserve(BATCH); hb.cigar.reserve(BATCH * 2);
+            }
+        }
+        BamReader &bam = *in.reader;
+        int cur = 0; bool in_flight = false;
+        for (;;) {
+            HostBatch &hb = S.bufs[cur];
+            hb.clear();
+            hb.file_index_base = alignmentCount;
+            const size_t n = bam.read_batch(hb, BATCH);              // decode overlaps the previous batch on the GPU
+            if (in_flight) { if ((rc = rsqc_wait(gpu)) != RSQC_OK) break; in_flight = false; }
+            if (n == 0) break;
+            if (o.verbosity) for (auto &nm : hb.bad_refid) cerr << S.prefix << "Unrecognized RefID on alignment: " << nm << endl;
+            bool revisit = false;
+            for (int32_t t : hb.seg_tid) visit_contig(t, revisit);
+            if (hb.unsorted || revisit) warn_unsorted();
+            alignmentCount += n;
+            row.records = alignmentCount;
+            rsqc_batch view = hb.view();
+            if ((rc = rsqc_submit(gpu, &view)) != RSQC_OK) break;
+            in_flight = true;
+            cur ^= 1;
+            if (o.verbosity > 1) cout << "Alignments processed: " << alignmentCount << endl;
+        }
+    }
+    rsqc_results res{};
+    if (rc == RSQC_OK) rc = rsqc_finalize(gpu, &res);
+    S.t_loop1 = Clock::now();
+    if (rc == RSQC_ERR_BAD_CIGAR) throw std::invalid_argument("Unrecognized Cigar Op ");
+    if (rc == RSQC_ERR_EMPTY_MEDIAN) throw std::range_error("Cannot compute median of an empty list");
+    if (rc != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    S.dirty = false; S.needs_reset = true;
+    if (o.verbosity) {
+        const double secs = seconds_between(S.t_loop0, S.t_loop1);
+        cout << "Time Elapsed: " << secs << "; Alignments processed: " << alignmentCount << endl;
+        if (o.verbosity > 1) cout << "Average Reads/Sec: " << (double)alignmentCount / secs << endl;
+        if (o.verbosity > 1 && sam_input) cout << "(decode: " << (in.fmt == InputFormat::SamBgzf ? "BGZF inflate and SAM text parsing" : "SAM text") << " on the GPU)" << endl;
+        else if (o.verbosity > 1 && device_decode) cout << "(decode: BGZF inflate and record parsing on the GPU)" << endl;
+        else if (o.verbosity > 1) cout << "(decode threads: " << in.reader->inflate_threads() << " inflate + " << in.reader->parse_threads() << " parse)" << endl;
+        cout << "Estimating library complexity..." << endl;
+        cout << "Generating report" << endl;
+    }
+    ReportConfig cfg;
+    cfg.output_dir = out_dir; cfg.sample_name = sample.name; cfg.sample_given = sample.name_given;
+    cfg.use_rpkm = o.rpkm; cfg.write_coverage = o.coverage; cfg.detection_threshold = (unsigned)o.detection;
+    cfg.filter_tags = o.tags;
+    if (!S.async_reports) {
+        S.t_rep0 = Clock::now();
+        write_reports(cfg, ann, res, visit);
+        S.t_rep1 = Clock::now();
+        return 0;
+    }
+    // a cohort: the writer gets a copy of what it reads, the context goes on to the next sample.  The row is the job's from
+    // here on (the caller reads it after finish_reports()).
+    S.finish_reports();
+    timer.armed = false;
+    std::shared_ptr<ResultsCopy> copy(new ResultsCopy(res));
+    const std::string prefix = S.prefix;
+    S.report_job = std::async(std::launch::async, [cfg, &ann, copy, visit, &row, t_open, prefix] {
+        try { write_reports(cfg, ann, copy->res, visit); }
+        catch (...) { row.exit_code = explain_exception(prefix); }
+        row.seconds = seconds_between(t_open, Clock::now());
+    });
+    return 0;
+}
+
+// ---- --bam-list: the samples of a list through one context, back to back
+struct ListError : std::runtime_error { using std::runtime_error::runtime_error; };      // exit 10: the list file itself
+
+std::vector<Sample> read_bam_list(const std::string &list_path) {
+    std::ifstream f(list_path);
+    if (!f.is_open()) throw ListError("Unable to open the sample list: " + list_path);
+    const size_t slash = list_path.find_last_of('/');
+    const std::string dir = slash == std::string::npos ? "" : list_path.substr(0, slash + 1);
+    std::vector<Sample> samples;
+    std::string line;
+    while (std::getline(f, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const size_t tab = line.find('\t');
+        Sample s;
+        s.path = line.substr(0, tab);
+        if (s.path.empty()) continue;
+        s.name = tab == std::string::npos ? "" : line.substr(tab + 1);
+        s.name_given = !s.name.empty();
+        if (s.name.empty()) s.name = basename_of(s.path);                  // the one-sample rule: the path's basename
+        if (s.path[0] != '/') s.path = dir + s.path;
+        samples.push_back(std::move(s));
+    }
+    if (samples.empty()) throw ValidationError("The sample list is empty: " + list_path);
+    std::map<std::string, int> seen;
+    for (auto &s : samples) if (seen[s.name]++) throw ValidationError("Sample name appears twice in the list: " + s.name);
+    return samples;
+}
+
+int run_cohort(const Options &o, Annotation &ann, Session &S, std::vector<Sample> &samples, const std::string &out_dir) {
+    using std::cerr; using std::endl;
+    std::vector<SampleRow> rows(samples.size());
+    S.async_reports = true;
+    S.keep_fasta = true;
+    const Options *op = &o;
+    auto open_ahead = [op](Sample &s) { const std::string p = s.path; s.opened = std::async(std::launch::async, [p, op] { return open_input(p, *op); }); };
+    open_ahead(samples[0]);
+    for (size_t k = 0; k < samples.size(); ++k) {
+        // the next sample is opened, sniffed and its header read beside this one's decode; none of its records is submitted
+        // before this one has been finalized and the context reset (run_sample)
+        if (k + 1 < samples.size()) open_ahead(samples[k + 1]);
+        SampleRow &row = rows[k];
+        row.sample = samples[k].name; row.input = samples[k].path;
+        S.prefix = samples[k].name + ": ";
+        int code;
+        try { code = run_sample(o, ann, S, samples[k], out_dir, row); }
+        catch (...) { code = explain_exception(S.prefix); }
+        if (code) row.exit_code = code;
+        if (row.fatal) {                                // a GPU failure: nothing further is started on the device
+            cerr << "Stopping after " << samples[k].name << ": the GPU failed; " << samples.size() - k - 1 << " samples were not run" << endl;
+            break;
+        }
+    }
+    S.finish_reports();
+    int first = 0; bool stopped = false;
+    std::ofstream t(out_dir + "/cohort.tsv");
+    t << "sample\tinput\tformat\trecords\tseconds\texit_code\n";
+    for (size_t k = 0; k < samples.size(); ++k) {
+        SampleRow &row = rows[k];
+        if (stopped) { row.sample = samples[k].name; row.input = samples[k].path; row.exit_code = 10; }
+        t << row.sample << '\t' << row.input << '\t' << row.format << '\t' << row.records << '\t' << row.seconds << '\t' << row.exit_code << '\n';
+        if (row.exit_code && !first) first = row.exit_code;
+        if (row.fatal) stopped = true;
+    }
+    return first;
+}
+
+// ---- `--gpus N`: one input sharded by contig over several contexts (the first is the session's); the header has been checked and
+// the annotation flattened for it, `bam` holds the index
+struct ShardedRun { const Options &o; Annotation &ann; Session &S; Input &in; const std::vector<int> &devices; BamReader &bam; std::string out_dir, sample_name; };
+int run_sharded(ShardedRun R) {
+    using std::cerr; using std::cout; using std::endl;
+    const Options &o = R.o; Annotation &ann = R.ann; Session &S = R.S; BamReader &bam = R.bam;
+    const std::string &bam_path = R.in.path;
+    const rsqc_params &P = S.P;
+    const int n_ref_bam = (int)R.in.contigs.size();
+    R.in.reader.reset();                                             // (every shard's thread opens the file itself)
+    std::vector<Shard> shards(R.devices.size());
+    uint64_t tail_voff = 0;
+    {
+        // longest-processing-time packing of the contigs on the index's record counts (compressed bytes when an index
+        // carries no counts); the unplaced tail goes to the lightest shard
+        const auto &idx = bam.index();
+        std::vector<std::pair<uint64_t, int>> byload;
+        for (int c2 = 0; c2 < n_ref_bam && (size_t)c2 < idx.size(); ++c2) if (idx[(size_t)c2].present) {
+            const uint64_t load = idx[(size_t)c2].n_records ? idx[(size_t)c2].n_records : ((idx[(size_t)c2].end >> 16) - (idx[(size_t)c2].beg >> 16)) / 24 + 1;
+            byload.emplace_back(load, c2);
+            tail_voff = std::max(tail_voff, idx[(size_t)c2].end);
+        }
+        std::sort(byload.begin(), byload.end(), [](const std::pair<uint64_t, int> &x, const std::pair<uint64_t, int> &y) { return x.first != y.first ? x.first > y.first : x.second < y.second; });
+        for (auto &bl : byload) {
+            size_t best = 0;
+            for (size_t g = 1; g < shards.size(); ++g) if (shards[g].load < shards[best].load) best = g;
+            shards[best].contigs.push_back(bl.second); shards[best].load += bl.first;
+        }
+        size_t lightest = 0;
+        for (size_t g = 1; g < shards.size(); ++g) if (shards[g].load < shards[lightest].load) lightest = g;
+        shards[lightest].tail = true;
+        for (auto &sh : shards) std::sort(sh.contigs.begin(), sh.contigs.end());
+    }
+    S.t_gpu0 = Clock::now();
+    int rc = S.gpu_ready.get();
+    S.t_gpu1 = Clock::now();
+    if (rc != RSQC_OK) { cerr << "Unable to initialise the GPU hot path: " << rsqc_strerror(rc) << endl; return 10; }
+    // (every exit below releases the contexts of the other shards and the exchange group; the first context is the session's)
+    rsqc_group *xgroup = nullptr;
+    std::future<int> group_ready;
+    struct Release { std::vector<Shard> &shards; rsqc_group *&xgroup; std::future<int> &group_ready;
+                     ~Release() { if (group_ready.valid()) (void)group_ready.get(); rsqc_group_destroy(xgroup); for (size_t g = 1; g < shards.size(); ++g) if (shards[g].gpu) rsqc_destroy(shards[g].gpu); } } release{shards, xgroup, group_ready};
+    std::vector<std::vector<uint8_t>> owned_masks(shards.size());
+    for (size_t g = 0; g < shards.size(); ++g) {
+        Shard &sh = shards[g];
+        sh.device = R.devices[g];
+        if (g == 0) sh.gpu = S.gpu;
+        else { rsqc_params Pg = P; Pg.device = sh.device; if ((rc = rsqc_create(&Pg, &sh.gpu)) != RSQC_OK) { cerr << "Unable to initialise GPU " << sh.device << ": " << rsqc_strerror(rc) << endl; return 10; } }
+    }
+    // the exchange group: the RCCL communicators come up HERE, on a thread beside the annotation upload and
+    // the feeders' set-up -- not inside the `Average Reads/Sec` window that the end-of-file reduction belongs to
+    {
+        std::vector<rsqc_ctx *> members;
+        for (auto &sh : shards) members.push_back(sh.gpu);
+        group_ready = std::async(std::launch::async, [members, &xgroup]() mutable { return rsqc_group_create(members.data(), (int)members.size(), &xgroup); });
+    }
+    std::vector<rsqc_ctx *> ctxs;
+    for (size_t g = 0; g < shards.size(); ++g) {
+        Shard &sh = shards[g];
+        owned_masks[g].assign(ann.contig_names.size(), 0);
+        for (int c2 : sh.contigs) owned_masks[g][(size_t)c2] = 1;
+        if (int code = set_annotation_and_bed(o, ann, sh.gpu, owned_masks[g].data(), g == 0, "", rc)) return code;
+        ctxs.push_back(sh.gpu);
+    }
+    if (o.has_fasta) if (int code = set_reference(S, ann, ctxs, rc)) return code;
+
+    // device decode needs exact range ends from the index
+    bool device_decode = device_decode_wanted(R.in.is_stream);
+    if (device_decode) for (auto &r : bam.index()) if (r.present && !r.end) device_decode = false;
+    if (device_decode && !(getenv("RSQC_DECODE_PRERESERVE") && !atoi(getenv("RSQC_DECODE_PRERESERVE")))) {
+        // the device's window buffers are set up before the loop, like the host path's page-locked batches
+        for (auto &sh : shards) {
+            rsqc_decode_params dp = decode_params(o, n_ref_bam, 0);
+            dp.reserve_inflated_bytes = decode_reserve_bytes(R.in.file_size);
+            rsqc_decode_info none{};
+            if ((rc = rsqc_decode_begin(sh.gpu, &dp)) != RSQC_OK || (rc = rsqc_decode_end(sh.gpu, &none)) != RSQC_OK) {
+                cerr << "Unable to set up the device decode: " << rsqc_last_error(sh.gpu) << endl; return 10;
+            }
+        }
+    }
+    // the feeders' chunk buffers are page-locked here, before the loop (see run_sample)
+    std::vector<std::unique_ptr<BgzfFeeder>> feeders;
+    if (device_decode) {
+        const int cpu_share_threads = feeder_cpu_threads();
+        for (size_t g = 0; g < shards.size(); ++g) {
+            feeders.emplace_back(new BgzfFeeder());
+            if (!feeders.back()->open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
+            if (cpu_share_threads > 0)             // (a shard's calls are a contig at a time: a fraction of the room)
+                feeders.back()->set_cpu_share(std::max(1, cpu_share_threads / (int)shards.size()), 0.15, 0.5, ((uint64_t)1 << 30) / shards.size());
+            if (feeder_prepin()) feeders.back()->reserve(std::max<size_t>(feeder_chunk_bytes() / shards.size(), (size_t)16 << 20));
+        }
+        feeders[0]->read_threads = getenv("RSQC_FEED_READ_THREADS") ? std::max(1, atoi(getenv("RSQC_FEED_READ_THREADS"))) : std::max(1, std::min(8, effective_cpus() / 2));
+    }
+    if (o.verbosity) cout << "Parsing bam..." << endl;
+    const size_t BATCH = getenv("RSQC_BATCH") ? (size_t)atol(getenv("RSQC_BATCH")) : (size_t)1 << 21;
+    std::vector<int> visit;
+    unsigned long long alignmentCount = 0;
+    bool warned_unsorted = false;
+    ShardMerge merged;
+    double group_init_ms = 0.0;
+    {                                                        // (before the window opens)
+        if ((rc = group_ready.get()) != RSQC_OK) { cerr << "Unable to set up the multi-GPU exchange: " << rsqc_strerror(rc) << endl; return 10; }
+        int uses = 0; const char *note = "";
+        rsqc_group_info(xgroup, &uses, &group_init_ms, nullptr, &note);
+        if (o.verbosity > 1) cout << "Exchange group of " << shards.size() << " GPUs ready in " << group_init_ms << " ms ("
+                                  << (uses ? "RCCL communicators" : (std::string("peer copies: ") + note).c_str()) << "), before the BAM loop" << endl;
+    }
+    const Clock::time_point tb0 = Clock::now();
+    {
+        // one reader thread per GPU; the decode threads of the process are shared out between them
+        int budget = 2 * effective_cpus();
+        if (const char *e = getenv("RSQC_HOST_THREADS")) budget = atoi(e);
+        const int per = std::max(2, budget / (int)shards.size());
+        std::vector<std::thread> th;
+        for (auto &sh : shards) th.emplace_back(shard_worker, std::ref(sh), std::cref(bam_path), std::cref(o), per, std::cref(bam.index()), n_ref_bam, tail_voff, BATCH, device_decode ? feeders[(size_t)(&sh - shards.data())].get() : nullptr);
+        for (auto &t : th) t.join();
+    }
+    rc = RSQC_OK;
+    for (auto &sh : shards) {
+        alignmentCount += sh.n_records;
+        if (sh.rc != RSQC_OK && rc == RSQC_OK) { rc = sh.rc; if (rc != RSQC_ERR_BAD_CIGAR && rc != RSQC_ERR_EMPTY_MEDIAN) cerr << "GPU " << sh.device << ": " << sh.error << endl; }
+        if (o.verbosity) for (auto &nm : sh.bad_refid) cerr << "Unrecognized RefID on alignment: " << nm << endl;
+        if (sh.unsorted && !warned_unsorted) { cerr << kUnsortedWarning << endl; warned_unsorted = true; }
+    }
+    for (int c2 = 0; c2 < n_ref_bam && (size_t)c2 < bam.index().size(); ++c2) if (bam.index()[(size_t)c2].present) {
+        visit.push_back(c2);
+        if (o.has_fasta && (size_t)c2 < S.in_fasta.size() && !S.in_fasta[(size_t)c2])
+            cerr << "Warning: Provided Fasta does not contain chromosome " << ann.contig_names[(size_t)c2]
+                 << ". No GC statistics will be collected for this chromosome" << endl;
+    }
+    // the exchange step: result ranges summed onto the first GPU, order-dependent outputs composed from the summaries
+    int used_rccl = 0;
+    if (rc == RSQC_OK) {
+        rc = rsqc_group_reduce(xgroup, &used_rccl);
+        if (rc != RSQC_OK) cerr << rsqc_last_error(shards[0].gpu) << endl;
+    }
+    if (rc == RSQC_OK) { std::string merr; rc = merge_shards(shards, P.fragment_samples, merged, merr); if (rc != RSQC_OK) cerr << merr << endl; }
+    if (o.verbosity > 1) {
+        cout << "Alignments processed: " << alignmentCount << " on " << shards.size() << " GPUs (";
+        for (size_t g = 0; g < shards.size(); ++g) cout << (g ? ", " : "") << shards[g].n_records;
+        double reduce_ms = 0.0; rsqc_group_info(xgroup, nullptr, nullptr, &reduce_ms, nullptr);
+        cout << " records); shards summed by " << (used_rccl ? "RCCL ncclReduce" : "peer copies") << " in " << reduce_ms << " ms (group set-up " << group_init_ms << " ms, outside the window)" << endl;
+    }
+    rsqc_results res{};
+    if (rc == RSQC_OK) {
+        rc = rsqc_refresh_results(S.gpu, &res);
+        res.read_length = merged.read_length;
+        res.n_fragment_sizes = (uint32_t)merged.fsize.size(); res.fragment_size = merged.fsize.data(); res.fragment_count = merged.fcount.data();
+        res.fragment_samples_remaining = merged.remaining;
+    }
+    const Clock::time_point tb1 = Clock::now();
+    if (rc == RSQC_ERR_BAD_CIGAR) throw std::invalid_argument("Unrecognized Cigar Op ");
+    if (rc == RSQC_ERR_EMPTY_MEDIAN) throw std::range_error("Cannot compute median of an empty list");
+    if (rc != RSQC_OK) { cerr << rsqc_strerror(rc) << ": " << rsqc_last_error(S.gpu) << endl; return 10; }
+    if (o.verbosity) {
+        const double secs = seconds_between(tb0, tb1);
+        cout << "Time Elapsed: " << secs << "; Alignments processed: " << alignmentCount << endl;
+        if (o.verbosity > 1) cout << "Average Reads/Sec: " << (double)alignmentCount / secs << endl;
+        if (o.verbosity > 1 && device_decode) cout << "(decode: BGZF inflate and record parsing on the GPU)" << endl;
+        cout << "Estimating library complexity..." << endl;
+        cout << "Generating report" << endl;
+    }
+    ReportConfig cfg;
+    cfg.output_dir = R.out_dir; cfg.sample_name = R.sample_name; cfg.sample_given = o.has_sample;
+    cfg.use_rpkm = o.rpkm; cfg.write_coverage = o.coverage; cfg.detection_threshold = (unsigned)o.detection;
+    cfg.filter_tags = o.tags;
+    const Clock::time_point tr0 = Clock::now();
+    write_reports(cfg, ann, res, visit);
+    const Clock::time_point tr1 = Clock::now();
+    if (group_ready.valid()) (void)group_ready.get();
+    rsqc_group_destroy(xgroup); xgroup = nullptr;
+    for (auto &sh : shards) { rsqc_destroy(sh.gpu); sh.gpu = nullptr; }
+    S.gpu = nullptr;                                                       // (shard 0's context was the session's)
+    if (o.verbosity > 1)
+        // where the wall time outside the reference's `Average Reads/Sec` window goes (extension; the window itself is above)
+        cout << "Wall time: " << seconds_between(S.t_start, Clock::now()) << " s = GTF " << seconds_between(S.t_gtf0, S.t_gtf1)
+             << " + waiting for the GPU context " << seconds_between(S.t_gpu0, S.t_gpu1) << " + index / annotation upload / buffers " << seconds_between(S.t_gpu1, tb0)
+             << " + BAM loop " << seconds_between(tb0, tb1) << " + reports " << seconds_between(tr0, tr1) << " + release " << seconds_between(tr1, Clock::now())
+             << " (the GPU context and the page-locked feed buffers come up beside the GTF parse)" << endl;
+    return 0;
+}
+
+}  // namespace
+
 int main(int argc, char **argv) {
     using std::cerr; using std::cout; using std::endl;
+    Session S;
+    int code = 0;
     try {
         Options o = parse(argc, argv);
         if (o.version) { cout << VERSION << endl; return 0; }
+        const size_t n_pos = o.has_bam_list ? 2 : 3;
         if (o.positional.size() < 1) throw ValidationError("No GTF file provided");
-        if (o.positional.size() < 2) throw ValidationError("No BAM file provided");
-        if (o.positional.size() < 3) throw ValidationError("No output directory provided");
-        if (o.positional.size() > 3) throw ParseError("Passed in argument, but no positional arguments were ready to receive it: " + o.positional[3]);
-        const std::string gtf_path = o.positional[0], bam_path = o.positional[1], out_dir = o.positional[2];
+        if (!o.has_bam_list && o.positional.size() < 2) throw ValidationError("No BAM file provided");
+        if (o.positional.size() < n_pos) throw ValidationError("No output directory provided");
+        if (o.positional.size() > n_pos) throw ParseError("Passed in argument, but no positional arguments were ready to receive it: " + o.positional[n_pos]);
+        const std::string gtf_path = o.positional[0], bam_path = o.has_bam_list ? "" : o.positional[1], out_dir = o.positional[n_pos - 1];
         int strand = RSQC_STRAND_UNKNOWN;
         if (o.has_stranded) {
             if (o.stranded == "RF" || o.stranded == "rf") strand = RSQC_STRAND_REVERSE;
             else if (o.stranded == "FR" || o.stranded == "fr") strand = RSQC_STRAND_FORWARD;
             else throw ValidationError("--stranded argument must be in {'RF', 'rf', 'FR', 'fr'}");
         }
+        // a cohort: the list is read and checked before anything else is touched
+        std::vector<Sample> samples;
+        if (o.has_bam_list) {
+            if (o.has_sample) throw ValidationError("--sample cannot name the samples of a --bam-list (give the names in the list's second column)");
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--bam-list runs on one GPU (--gpus, RSQC_GPUS and RSQC_GPU_LIST shard ONE input)");
+            try { samples = read_bam_list(o.bam_list); }
+            catch (ListError &e) { cerr << e.what() << endl; return 10; }
+        }
         if (o.tags.size() > RSQC_MAX_FILTER_TAGS) { cerr << "at most " << RSQC_MAX_FILTER_TAGS << " --tag filters are supported" << endl; return 7; }
 
-        rsqc_params P{};
+        rsqc_params &P = S.P;
         P.abi_version = RSQC_ABI_VERSION;
         P.device = getenv("RSQC_DEVICE") ? atoi(getenv("RSQC_DEVICE")) : 0;
         if (const char *e = getenv("RSQC_GPU_LIST")) if (*e) P.device = atoi(e);       // the first shard's context runs on the list's first device
@@ -392,55 +1141,42 @@ int main(int argc, char **argv) {
         P.bias_offset = (int32_t)o.bias_offset; P.bias_window = (int32_t)o.bias_window; P.bias_gene_length = o.bias_gene_length;
         P.coverage_mask = (uint32_t)o.coverage_mask; P.stranded = strand; P.unpaired = o.unpaired; P.exclude_chimeric = o.exclude_chimeric;
         P.n_filter_tags = (int32_t)o.tags.size();
-        const std::string SAMPLENAME = o.has_sample ? o.sample : basename_of(bam_path);
 
         // the HIP context comes up (~0.3 s) while the GTF is being parsed; its status is looked at where the
         // reference would first need it, so input errors keep their precedence and exit codes
-        rsqc_ctx *gpu = nullptr;
-        std::future<int> gpu_ready = std::async(std::launch::async, [&P, &gpu] { return rsqc_create(&P, &gpu); });
-        // ... and so do the page-locked chunk buffers of the device decode's feeder (one GPU: ~1.3 GB, a few hundred ms of
-        // page-locking that would otherwise sit between the GTF and the BAM loop).  A file that cannot be opened is reported
-        // later, where the reference reports it.
-        const auto t_start = std::chrono::steady_clock::now();
-        { struct stat st_in; g_input_is_stream = stat(bam_path.c_str(), &st_in) == 0 && !S_ISREG(st_in.st_mode); }
-        // the input's format by its content (a stream is sniffed where it is opened, below)
-        const InputFormat file_fmt = g_input_is_stream ? InputFormat::Unknown : sniff_file(bam_path);
-        auto feeder_cpu_threads = [] {
-            const int spare = effective_cpus() - 4;
-            return getenv("RSQC_DECODE_CPU_THREADS") ? atoi(getenv("RSQC_DECODE_CPU_THREADS")) : (spare >= 4 ? spare : 0);
-        };
-        const size_t feeder_chunk = getenv("RSQC_DECODE_CHUNK") ? (size_t)atoll(getenv("RSQC_DECODE_CHUNK")) : (size_t)512 << 20;
-        const bool feeder_prepin = !(getenv("RSQC_FEED_PREPIN") && !atoi(getenv("RSQC_FEED_PREPIN")));
-        std::unique_ptr<BgzfFeeder> early_feed;
-        std::future<bool> early_feed_ready;
-        if (device_decode_wanted() && file_fmt == InputFormat::Bam && feeder_prepin && o.gpus <= 1 && !getenv("RSQC_GPUS") && !getenv("RSQC_GPU_LIST")) {
-            early_feed.reset(new BgzfFeeder());
-            BgzfFeeder *ef = early_feed.get();
-            const int ct = feeder_cpu_threads();
-            const uint64_t feeder_max_out = getenv("RSQC_DECODE_MAX_OUT") ? (uint64_t)atoll(getenv("RSQC_DECODE_MAX_OUT")) : (uint64_t)1024 << 20;
-            early_feed_ready = std::async(std::launch::async, [ef, bam_path, ct, feeder_chunk, feeder_max_out] {
-                try {
-                    if (!ef->open(bam_path)) return false;
-                    // (the room behind a chunk's file bytes is page-locked for the largest share the CPUs can reach: 12 threads have
-                    //  settled at 0.10-0.25 of a call on every file measured; 0.5 only where there are the threads for it)
-                    if (ct > 0) ef->set_cpu_share(ct, 0.15, std::min(0.5, std::max(0.1, 0.025 * ct)), feeder_max_out);
-                    ef->reserve(feeder_chunk, feeder_max_out);
-                    return true;
-                } catch (std::exception &) { return false; }
-            });
+        {
+            Session *sp = &S;
+            S.gpu_ready = std::async(std::launch::async, [sp] { return rsqc_create(&sp->P, &sp->gpu); });
         }
-        const auto t0 = std::chrono::steady_clock::now();
+        // ... and so do the page-locked chunk buffers of the device decode's feeder: sized for the input, or for the largest
+        // BAM of a cohort (every later file goes through the same buffers)
+        S.t_start = Clock::now();
+        {
+            std::string feed_for;
+            if (!o.has_bam_list) {
+                struct stat st;
+                const bool is_stream = stat(bam_path.c_str(), &st) == 0 && !S_ISREG(st.st_mode);
+                if (device_decode_wanted(is_stream) && sniff_file(bam_path) == InputFormat::Bam && o.gpus <= 1 && !getenv("RSQC_GPUS") && !getenv("RSQC_GPU_LIST")) feed_for = bam_path;
+            } else {
+                for (auto &s : samples) {
+                    struct stat st;
+                    if (stat(s.path.c_str(), &st) != 0 || !S_ISREG(st.st_mode) || (uint64_t)st.st_size <= S.reserve_file_size) continue;
+                    if (!device_decode_wanted(false) || sniff_file(s.path) != InputFormat::Bam) continue;
+                    S.reserve_file_size = (uint64_t)st.st_size; feed_for = s.path;
+                }
+            }
+            if (!feed_for.empty() && feeder_prepin()) start_early_feeder(S, feed_for);
+        }
+        S.t_gtf0 = Clock::now();
         Annotation ann;
         ann.legacy = o.legacy;
-        FastaFile fasta;
-        std::vector<std::vector<uint8_t>> fasta_seq;
-        std::future<void> fasta_loaded;                                       // (declared last: its destructor joins the reader before the buffers go)
         if (o.has_fasta) {                                                    // src/RNASeQC.cpp:111-121: GTF openable, then Fasta::open
             { std::ifstream probe(gtf_path); if (!probe.is_open()) { cerr << "Unable to open GTF file: " << gtf_path << endl; return 10; } }
-            fasta.open(o.fasta);                                              // FileError -> 10
-            for (auto &e : fasta.index) ann.chromosome(e.name);               // the index names join chromosomeMap first (src/Fasta.cpp:93-94)
+            S.fasta.open(o.fasta);                                            // FileError -> 10
+            for (auto &e : S.fasta.index) ann.chromosome(e.name);             // the index names join chromosomeMap first (src/Fasta.cpp:93-94)
             if (o.verbosity > 1) cout << "A FASTA has been provided. This will enable GC-content statistics but adds additional runtime and memory costs" << endl;
-            fasta_loaded = std::async(std::launch::async, [&fasta, &fasta_seq] { fasta.load(fasta_seq); });   // read beside the GTF parse
+            Session *sp = &S;
+            S.fasta_loaded = std::async(std::launch::async, [sp] { sp->fasta.load(sp->fasta_seq); });   // read beside the GTF parse
         }
         if (o.verbosity) cout << "Reading GTF Features..." << endl;
         ann.load_gtf(gtf_path);                                               // FileError -> 10, GtfError -> 11
@@ -449,481 +1185,73 @@ int main(int argc, char **argv) {
             cerr << ann.gene_list.size() << " genes parsed" << endl << ann.exon_list.size() << " exons parsed" << endl;
             return 11;
         }
-        const auto t1 = std::chrono::steady_clock::now();
-        if (o.verbosity) cout << "Finished processing GTF in " << std::chrono::duration<double>(t1 - t0).count() << " seconds" << endl;
-        std::vector<char> gtf_chrom(ann.chrom_name.size() + 1, 0);
-        for (auto &r : ann.rows) if (!r.excluded) gtf_chrom[(size_t)r.chrom] = 1;
+        S.t_gtf1 = Clock::now();
+        if (o.verbosity) cout << "Finished processing GTF in " << seconds_between(S.t_gtf0, S.t_gtf1) << " seconds" << endl;
+        S.gtf_chrom.assign(ann.chrom_name.size() + 1, 0);
+        for (auto &r : ann.rows) if (!r.excluded) S.gtf_chrom[(size_t)r.chrom] = 1;
         if (o.has_bed) {
             if (o.verbosity) cout << "Parsing BED intervals for fragment size computations..." << endl;
             ann.load_bed(o.bed);
         }
+        S.base_chrom_id = ann.chrom_id; S.base_chrom_name = ann.chrom_name;
         if (!make_dirs(out_dir)) { cerr << "Filesystem error:  cannot create " << out_dir << endl; return 8; }
-        // The header: with the device decode (the default) the host only inflates the header's own blocks; the multi-threaded
-        // CPU reader (whose pools start inflating the file as soon as it is opened) comes up only for RSQC_DECODE=host.
-        BamReader bam;
-        std::vector<std::string> bam_contigs;
-        uint64_t first_voff = 0;
-        bool bam_open = false;
-        // SAM input (plain or BGZF-compressed): the header's @SQ lines are read here, the text goes to the device SAM stages
-        InputFormat in_fmt = file_fmt;
-        std::string reader_path = bam_path;                                   // what the host BAM reader opens
-        std::unique_ptr<SamTextFeeder> sam_feed;
-        if (g_input_is_stream) {
-            // a FIFO / stdin: its first bytes are read to tell the format and stay the first chunk's; a BAM is handed on to the
-            // host reader through a pipe of this process that replays them
-            sam_feed.reset(new SamTextFeeder());
-            if (!sam_feed->open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-            const std::vector<uint8_t> &first = sam_feed->peek(1 << 16);
-            in_fmt = sniff_format(first.data(), first.size());
-            if (in_fmt == InputFormat::Bam || in_fmt == InputFormat::Unknown) {
-                int pfd[2];
-                if (pipe(pfd) != 0) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-                signal(SIGPIPE, SIG_IGN);
-                const int src = sam_feed->release_fd();
-                std::thread([src, pfd, head = sam_feed->peek(0)]() {
-                    auto put = [&](const uint8_t *b, size_t n) { while (n) { const ssize_t w = write(pfd[1], b, n); if (w <= 0) return false; b += w; n -= (size_t)w; } return true; };
-                    bool ok = put(head.data(), head.size());
-                    std::vector<uint8_t> buf(1 << 20);
-                    while (ok) { const ssize_t g = read(src, buf.data(), buf.size()); if (g <= 0) break; ok = put(buf.data(), (size_t)g); }
-                    close(pfd[1]); close(src);
-                }).detach();
-                reader_path = "/dev/fd/" + std::to_string(pfd[0]);
-                sam_feed.reset();
-                in_fmt = InputFormat::Bam;
-            }
-        }
-        if (in_fmt == InputFormat::PlainGzip) {
-            cerr << "Unable to open BAM file: " << bam_path << " (gzip-compressed but not BGZF: recompress it with bgzip)" << endl; return 10;
-        }
-        if (in_fmt == InputFormat::SamBgzf && g_input_is_stream) {
-            cerr << "Unable to open BAM file: " << bam_path << " (BGZF-compressed SAM is read from a regular file only: decompress it into the pipe)" << endl; return 10;
-        }
-        const bool sam_input = in_fmt == InputFormat::SamText || in_fmt == InputFormat::SamBgzf;
-        if (sam_input) {
-            SamHeader hdr;
-            if (sam_feed) {
-                bool complete = false;
-                for (size_t want = 1 << 16;; want *= 2) {
-                    const auto &hd = sam_feed->peek(want);
-                    hdr = SamHeader{};
-                    parse_sam_header((const char *)hd.data(), hd.size(), hdr, complete);
-                    if (complete || hd.size() < want) break;
-                }
-            } else if (!read_sam_header(bam_path, hdr)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-            bam_contigs = hdr.names;
-            if (o.verbosity > 1) cout << "Input: " << input_format_name(in_fmt) << " (" << hdr.names.size() << " @SQ lines), parsed on the GPU" << endl;
-        }
-        auto open_host_reader = [&]() -> bool {
-            if (bam_open) return true;
-            if (!bam.open(reader_path)) return false;
-            bam.set_tags(o.chimeric_tag, o.tags);
-            bam_open = true;
-            return true;
-        };
-        if (sam_input) {
-        } else if (device_decode_wanted()) {
-            BgzfFeeder probe;
-            if (!probe.open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-            try { first_voff = probe.first_record_voffset(&bam_contigs); }
-            catch (std::exception &) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-        } else {
-            if (!open_host_reader()) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-            bam_contigs = bam.contigs();
-        }
-        // header check: at least one BAM contig must carry GTF features (src/RNASeQC.cpp:216-238)
-        if (o.verbosity > 1) cout << "Checking bam header..." << endl;
-        bool overlap = false;
-        for (auto &n : bam_contigs) { auto it = ann.chrom_id.find(n); if (it != ann.chrom_id.end() && (size_t)it->second < gtf_chrom.size() && gtf_chrom[(size_t)it->second]) overlap = true; }
-        if (!overlap) { cerr << "BAM file shares no contigs with GTF" << endl; return 11; }
-        ann.flatten(bam_contigs);
 
-        // ---- GPUs: one by default; --gpus N (or RSQC_GPUS) shards the file by contig, which needs the BAM index
-        std::vector<int> devices;
-        {
-            int want = o.gpus > 0 ? o.gpus : (getenv("RSQC_GPUS") ? atoi(getenv("RSQC_GPUS")) : 1);
+        if (o.has_bam_list) code = run_cohort(o, ann, S, samples, out_dir);
+        else {
+            Sample sample;
+            sample.path = bam_path; sample.name = o.has_sample ? o.sample : basename_of(bam_path); sample.name_given = o.has_sample;
+            // ---- GPUs: one by default; --gpus N (or RSQC_GPUS) shards the file by contig, which needs the BAM index
+            std::vector<int> devices;
+            const int want = o.gpus > 0 ? o.gpus : (getenv("RSQC_GPUS") ? atoi(getenv("RSQC_GPUS")) : 1);
             if (const char *e = getenv("RSQC_GPU_LIST")) { for (const char *q = e; *q;) { devices.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q) ++q; } }
             else for (int k = 0; k < std::max(1, want); ++k) devices.push_back(P.device + k);
-            if (devices.size() > 1 && (sam_input || !bam.load_index(bam_path + ".bai"))) {       // (SAM has no index)
-                cerr << "Warning: sharding over " << devices.size() << " GPUs needs the BAM index " << bam_path << ".bai; running on one GPU" << endl;
-                devices.resize(1);
+            bool sharded = false;
+            std::unique_ptr<Input> in;
+            BamReader index_reader;
+            if (devices.size() > 1) {
+                in = open_input(bam_path, o);
+                if (!in->error.empty()) { cerr << in->error << endl; return 10; }
+                if (in->sam() && o.verbosity > 1) cout << "Input: " << input_format_name(in->fmt) << " (" << in->contigs.size() << " @SQ lines), parsed on the GPU" << endl;
+                if (o.verbosity > 1) cout << "Checking bam header..." << endl;
+                if (!shares_contigs(S, ann, in->contigs)) { cerr << "BAM file shares no contigs with GTF" << endl; return 11; }
+                flatten_for(S, ann, in->contigs);
+                if (in->sam() || !index_reader.load_index(bam_path + ".bai")) {        // (SAM has no index)
+                    cerr << "Warning: sharding over " << devices.size() << " GPUs needs the BAM index " << bam_path << ".bai; running on one GPU" << endl;
+                    devices.resize(1);
+                } else sharded = true;
             }
-        }
-        const int n_ref_bam = (int)bam_contigs.size();
-        std::vector<Shard> shards(devices.size());
-        uint64_t tail_voff = 0;
-        if (devices.size() > 1) {
-            // longest-processing-time packing of the contigs on the index's record counts (compressed bytes when an index
-            // carries no counts); the unplaced tail goes to the lightest shard
-            const auto &idx = bam.index();
-            std::vector<std::pair<uint64_t, int>> byload;
-            for (int c2 = 0; c2 < n_ref_bam && (size_t)c2 < idx.size(); ++c2) if (idx[(size_t)c2].present) {
-                const uint64_t load = idx[(size_t)c2].n_records ? idx[(size_t)c2].n_records : ((idx[(size_t)c2].end >> 16) - (idx[(size_t)c2].beg >> 16)) / 24 + 1;
-                byload.emplace_back(load, c2);
-                tail_voff = std::max(tail_voff, idx[(size_t)c2].end);
-            }
-            std::sort(byload.begin(), byload.end(), [](const std::pair<uint64_t, int> &x, const std::pair<uint64_t, int> &y) { return x.first != y.first ? x.first > y.first : x.second < y.second; });
-            for (auto &bl : byload) {
-                size_t best = 0;
-                for (size_t g = 1; g < shards.size(); ++g) if (shards[g].load < shards[best].load) best = g;
-                shards[best].contigs.push_back(bl.second); shards[best].load += bl.first;
-            }
-            size_t lightest = 0;
-            for (size_t g = 1; g < shards.size(); ++g) if (shards[g].load < shards[lightest].load) lightest = g;
-            shards[lightest].tail = true;
-            for (auto &sh : shards) std::sort(sh.contigs.begin(), sh.contigs.end());
-        }
-
-        const auto t_gpu0 = std::chrono::steady_clock::now();
-        int rc = gpu_ready.get();
-        const auto t_gpu1 = std::chrono::steady_clock::now();
-        if (rc != RSQC_OK) { cerr << "Unable to initialise the GPU hot path: " << rsqc_strerror(rc) << endl; return 10; }
-        std::vector<std::vector<uint8_t>> owned_masks(shards.size());
-        for (size_t g = 0; g < shards.size(); ++g) {
-            Shard &sh = shards[g];
-            sh.device = devices[g];
-            if (g == 0) sh.gpu = gpu;
-            else { rsqc_params Pg = P; Pg.device = sh.device; if ((rc = rsqc_create(&Pg, &sh.gpu)) != RSQC_OK) { cerr << "Unable to initialise GPU " << sh.device << ": " << rsqc_strerror(rc) << endl; return 10; } }
-        }
-        // the exchange group of a sharded run: the RCCL communicators come up HERE, on a thread beside the annotation upload and
-        // the feeders' set-up -- not inside the `Average Reads/Sec` window that the end-of-file reduction belongs to
-        rsqc_group *xgroup = nullptr;
-        std::future<int> group_ready;
-        if (shards.size() > 1) {
-            std::vector<rsqc_ctx *> members;
-            for (auto &sh : shards) members.push_back(sh.gpu);
-            group_ready = std::async(std::launch::async, [members, &xgroup]() mutable { return rsqc_group_create(members.data(), (int)members.size(), &xgroup); });
-        }
-        for (size_t g = 0; g < shards.size(); ++g) {
-            Shard &sh = shards[g];
-            const uint8_t *owned = nullptr;
-            if (shards.size() > 1) {
-                owned_masks[g].assign(ann.contig_names.size(), 0);
-                for (int c2 : sh.contigs) owned_masks[g][(size_t)c2] = 1;
-                owned = owned_masks[g].data();
-            }
-            if ((rc = rsqc_set_annotation(sh.gpu, &ann.ann, owned)) != RSQC_OK) {
-                // (the GTF parsed: this is the device index refusing the annotation -- e.g. no memory for the interval tables -- and
-                //  its own message says which)
-                cerr << "Unable to build the annotation index on the GPU: " << rsqc_last_error(sh.gpu) << endl; return 11;
-            }
-            // accepted with a warning (an exon outside its gene's row): the reference's counterpart is its per-read
-            // "Gene encountered after computing coverage" (src/Metrics.cpp:108-112); said once, before the BAM loop
-            if (g == 0 && rsqc_last_error(sh.gpu)[0]) cerr << "Warning: " << rsqc_last_error(sh.gpu) << endl;
-            if (o.has_bed && (rc = rsqc_set_bed(sh.gpu, &ann.bed)) != RSQC_OK) { cerr << "Failed to parse the BED: " << rsqc_last_error(sh.gpu) << endl; return 11; }
-        }
-        std::vector<char> in_fasta;
-        if (o.has_fasta) {
-            fasta_loaded.get();                                               // FileError -> 10
-            in_fasta.assign(ann.contig_names.size(), 0);
-            std::vector<int32_t> r_contig; std::vector<uint64_t> r_len; std::vector<const uint8_t *> r_seq;
-            for (size_t i = 0; i < fasta.index.size(); ++i) {
-                int cid = -1;
-                for (size_t k = 0; k < ann.contig_names.size(); ++k) if (ann.contig_names[k] == fasta.index[i].name) { cid = (int)k; break; }
-                if (cid < 0) continue;                                        // a contig neither the BAM nor the GTF/BED names
-                r_contig.push_back(cid); r_len.push_back(fasta_seq[i].size()); r_seq.push_back(fasta_seq[i].data());
-                in_fasta[(size_t)cid] = 1;
-            }
-            rsqc_reference ref{(int32_t)r_contig.size(), r_contig.data(), r_len.data(), r_seq.data()};
-            for (auto &sh : shards)
-                if ((rc = rsqc_set_reference(sh.gpu, &ref)) != RSQC_OK) { cerr << "Failed to load the reference: " << rsqc_last_error(sh.gpu) << endl; return 10; }
-            std::vector<std::vector<uint8_t>>().swap(fasta_seq);              // the bases live on the device now
-        }
-
-        // device decode needs exact range ends from the index when the file is sharded
-        bool device_decode = device_decode_wanted() && !sam_input;
-        if (device_decode && shards.size() > 1)
-            for (auto &r : bam.index()) if (r.present && !r.end) device_decode = false;
-        if (!sam_input && !device_decode && shards.size() == 1 && !open_host_reader()) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-        if (device_decode && !(getenv("RSQC_DECODE_PRERESERVE") && !atoi(getenv("RSQC_DECODE_PRERESERVE")))) {
-            // the device's window buffers are set up before the loop, like the host path's page-locked batches below
-            struct stat st{};
-            const uint64_t fsz = stat(bam_path.c_str(), &st) == 0 ? (uint64_t)st.st_size : 0;
-            for (auto &sh : shards) {
-                rsqc_decode_params dp = decode_params(o, n_ref_bam, 0);
-                dp.reserve_inflated_bytes = decode_reserve_bytes(fsz);
-                rsqc_decode_info none{};
-                if ((rc = rsqc_decode_begin(sh.gpu, &dp)) != RSQC_OK || (rc = rsqc_decode_end(sh.gpu, &none)) != RSQC_OK) {
-                    cerr << "Unable to set up the device decode: " << rsqc_last_error(sh.gpu) << endl; return 10;
+            if (sharded) code = run_sharded(ShardedRun{o, ann, S, *in, devices, index_reader, out_dir, sample.name});
+            else {
+                if (in) { std::promise<std::unique_ptr<Input>> ready; sample.opened = ready.get_future(); ready.set_value(std::move(in)); }
+                SampleRow row;
+                code = run_sample(o, ann, S, sample, out_dir, row);
+                if (code == 0 && o.verbosity > 1) {
+                    // where the wall time outside the reference's `Average Reads/Sec` window goes (extension; the window itself is above)
+                    const Clock::time_point t_rel0 = Clock::now();
+                    rsqc_destroy(S.gpu); S.gpu = nullptr;
+                    cout << "Wall time: " << seconds_between(S.t_start, Clock::now()) << " s = GTF " << seconds_between(S.t_gtf0, S.t_gtf1)
+                         << " + waiting for the GPU context " << seconds_between(S.t_gpu0, S.t_gpu1) << " + index / annotation upload / buffers " << seconds_between(S.t_gpu1, S.t_loop0)
+                         << " + BAM loop " << seconds_between(S.t_loop0, S.t_loop1) << " + reports " << seconds_between(S.t_rep0, S.t_rep1) << " + release " << seconds_between(t_rel0, Clock::now())
+                         << " (the GPU context and the page-locked feed buffers come up beside the GTF parse)" << endl;
                 }
             }
-        }
-        // the feeders' chunk buffers are page-locked here, before the loop: page-locking takes the HIP runtime's lock, and done
-        // by the read-ahead thread during the loop it stalled the thread that feeds the GPU (193 -> 237 M reads/s)
-        std::vector<std::unique_ptr<BgzfFeeder>> feeders;
-        if (device_decode) {
-            // RSQC_DECODE_CPU_THREADS=n: n spare CPU threads inflate the tail of every chunk beside the GPU (BgzfFeeder::set_cpu_share)
-            // (default: the CPUs the process may use minus four for the file reads and the thread that feeds the GPU; measured on the
-            //  16-CPU box, 12 threads: 258 -> 279 M reads/s, 85 -> 97 M on the realistic-entropy file, profiles/r2_decode_cpu_share_ab.txt)
-            const int cpu_share_threads = feeder_cpu_threads();
-            const bool early_ok = early_feed && early_feed_ready.valid() && early_feed_ready.get();
-            for (size_t g = 0; g < shards.size(); ++g) {
-                if (g == 0 && early_ok && shards.size() == 1) { feeders.push_back(std::move(early_feed)); continue; }
-                feeders.emplace_back(new BgzfFeeder());
-                if (!feeders.back()->open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-                if (cpu_share_threads > 0)             // (a shard's calls are a contig at a time: a fraction of the room)
-                    feeders.back()->set_cpu_share(std::max(1, cpu_share_threads / (int)shards.size()), 0.15, 0.5, ((uint64_t)1 << 30) / shards.size());
-                if (feeder_prepin) feeders.back()->reserve(shards.size() == 1 ? feeder_chunk : std::max<size_t>(feeder_chunk / shards.size(), (size_t)16 << 20));
-            }
-            // (threads that read one chunk's slices side by side; RSQC_FEED_READ_THREADS overrides)
-            feeders[0]->read_threads = getenv("RSQC_FEED_READ_THREADS") ? std::max(1, atoi(getenv("RSQC_FEED_READ_THREADS"))) : std::max(1, std::min(8, effective_cpus() / 2));
-        }
-        if (o.verbosity) cout << "Parsing bam..." << endl;
-        const size_t BATCH = getenv("RSQC_BATCH") ? (size_t)atol(getenv("RSQC_BATCH")) : (size_t)1 << 21;
-        HostBatch bufs[2];
-        for (auto &hb : bufs) {                                  // page-locked staging, sized once
-            hb.core.use_pinned(true); hb.aux.use_pinned(true); hb.qh2.use_pinned(true); hb.cigar.use_pinned(true);
-            hb.core.reserve(BATCH); hb.aux.reserve(BATCH); hb.qh2.reserve(BATCH); hb.cigar.reserve(BATCH * 2);
-        }
-        std::vector<int> visit;
-        unsigned long long alignmentCount = 0;
-        int cur = 0; bool in_flight = false, warned_unsorted = false;
-        ShardMerge merged;
-        double group_init_ms = 0.0;
-        if (group_ready.valid()) {                               // (before the window opens)
-            if ((rc = group_ready.get()) != RSQC_OK) { cerr << "Unable to set up the multi-GPU exchange: " << rsqc_strerror(rc) << endl; return 10; }
-            int uses = 0; const char *note = "";
-            rsqc_group_info(xgroup, &uses, &group_init_ms, nullptr, &note);
-            if (o.verbosity > 1) cout << "Exchange group of " << shards.size() << " GPUs ready in " << group_init_ms << " ms ("
-                                      << (uses ? "RCCL communicators" : (std::string("peer copies: ") + note).c_str()) << "), before the BAM loop" << endl;
-        }
-        const auto tb0 = std::chrono::steady_clock::now();
-        if (shards.size() > 1) {
-            // one reader thread per GPU; the decode threads of the process are shared out between them
-            int budget = 2 * effective_cpus();
-            if (const char *e = getenv("RSQC_HOST_THREADS")) budget = atoi(e);
-            const int per = std::max(2, budget / (int)shards.size());
-            std::vector<std::thread> th;
-            for (auto &sh : shards) th.emplace_back(shard_worker, std::ref(sh), std::cref(bam_path), std::cref(o), per, std::cref(bam.index()), n_ref_bam, tail_voff, BATCH, device_decode ? feeders[(size_t)(&sh - shards.data())].get() : nullptr);
-            for (auto &t : th) t.join();
-            rc = RSQC_OK;
-            for (auto &sh : shards) {
-                alignmentCount += sh.n_records;
-                if (sh.rc != RSQC_OK && rc == RSQC_OK) { rc = sh.rc; if (rc != RSQC_ERR_BAD_CIGAR && rc != RSQC_ERR_EMPTY_MEDIAN) cerr << "GPU " << sh.device << ": " << sh.error << endl; }
-                if (o.verbosity) for (auto &nm : sh.bad_refid) cerr << "Unrecognized RefID on alignment: " << nm << endl;
-                if (sh.unsorted && !warned_unsorted) { cerr << "Warning: The input bam does not appear to be sorted. An unsorted bam will yield incorrect results" << endl; warned_unsorted = true; }
-            }
-            for (int c2 = 0; c2 < n_ref_bam && (size_t)c2 < bam.index().size(); ++c2) if (bam.index()[(size_t)c2].present) {
-                visit.push_back(c2);
-                if (o.has_fasta && (size_t)c2 < in_fasta.size() && !in_fasta[(size_t)c2])
-                    cerr << "Warning: Provided Fasta does not contain chromosome " << ann.contig_names[(size_t)c2]
-                         << ". No GC statistics will be collected for this chromosome" << endl;
-            }
-            // the exchange step: result ranges summed onto the first GPU, order-dependent outputs composed from the summaries
-            int used_rccl = 0;
-            if (rc == RSQC_OK) {
-                rc = rsqc_group_reduce(xgroup, &used_rccl);
-                if (rc != RSQC_OK) cerr << rsqc_last_error(shards[0].gpu) << endl;
-            }
-            if (rc == RSQC_OK) { std::string merr; rc = merge_shards(shards, P.fragment_samples, merged, merr); if (rc != RSQC_OK) cerr << merr << endl; }
-            if (o.verbosity > 1) {
-                cout << "Alignments processed: " << alignmentCount << " on " << shards.size() << " GPUs (";
-                for (size_t g = 0; g < shards.size(); ++g) cout << (g ? ", " : "") << shards[g].n_records;
-                double reduce_ms = 0.0; rsqc_group_info(xgroup, nullptr, nullptr, &reduce_ms, nullptr);
-                cout << " records); shards summed by " << (used_rccl ? "RCCL ncclReduce" : "peer copies") << " in " << reduce_ms << " ms (group set-up " << group_init_ms << " ms, outside the window)" << endl;
-            }
-        } else if (sam_input) {
-            // ---- one GPU, SAM text: the host reads the file (plain) or frames its BGZF blocks, the device does the rest
-            rsqc_decode_info di{};
-            std::vector<const char *> names;
-            for (auto &nm : bam_contigs) names.push_back(nm.c_str());
-            auto on_window = [&](const rsqc_decode_window &w) {
-                bool revisit = false;
-                for (uint32_t k = 0; k < w.n_runs; ++k) {
-                    const int32_t t = w.run_tid[k];
-                    if (t < 0 || (!visit.empty() && visit.back() == t)) continue;
-                    if (std::find(visit.begin(), visit.end(), t) != visit.end()) revisit = true;
-                    visit.push_back(t);
-                    if (o.has_fasta && (size_t)t < in_fasta.size() && !in_fasta[(size_t)t])
-                        cerr << "Warning: Provided Fasta does not contain chromosome " << ann.contig_names[(size_t)t]
-                             << ". No GC statistics will be collected for this chromosome" << endl;
-                }
-                if (revisit && !warned_unsorted) {
-                    cerr << "Warning: The input bam does not appear to be sorted. An unsorted bam will yield incorrect results" << endl;
-                    warned_unsorted = true;
-                }
-                alignmentCount += w.n_records;
-                if (o.verbosity > 1) cout << "Alignments processed: " << alignmentCount << endl;
-            };
-            if (in_fmt == InputFormat::SamBgzf) {
-                BgzfFeeder feed;
-                if (!feed.open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-                feed.read_threads = std::max(1, std::min(8, effective_cpus() / 2));
-                rc = decode_range(gpu, feed, decode_params(o, n_ref_bam, 0), 0, 0, di, on_window, names.data());
-            } else {
-                if (!sam_feed) {
-                    sam_feed.reset(new SamTextFeeder());
-                    if (!sam_feed->open(bam_path)) { cerr << "Unable to open BAM file: " << bam_path << endl; return 10; }
-                }
-                // (RSQC_SAM_CHUNK: bytes of text per call; the tests use small values so that lines straddle many calls)
-                const size_t chunk = getenv("RSQC_SAM_CHUNK") ? (size_t)atoll(getenv("RSQC_SAM_CHUNK")) : (size_t)256 << 20;
-                rsqc_decode_params dp = decode_params(o, n_ref_bam, 0);
-                dp.pipelined = 1;
-                dp.reserve_inflated_bytes = chunk + (1u << 20);
-                rc = rsqc_decode_begin_sam(gpu, &dp, names.data());
-                if (rc == RSQC_OK) {
-                    sam_feed->start(chunk);
-                    while (SamTextFeeder::Chunk *ch = sam_feed->next()) {
-                        rsqc_decode_window w{};
-                        rc = rsqc_decode_submit_text(gpu, ch->data, ch->bytes, &w);
-                        if (rc != RSQC_OK) break;
-                        if (w.n_records) on_window(w);
-                    }
-                    if (rc != RSQC_OK) { rsqc_decode_info dropped{}; (void)rsqc_decode_end(gpu, &dropped); }
-                    else {
-                        if (!sam_feed->error().empty()) throw std::runtime_error(sam_feed->error());
-                        rc = rsqc_decode_end(gpu, &di);
-                        if (rc == RSQC_OK && di.last.n_records) on_window(di.last);
-                    }
-                }
-            }
-            if (rc == RSQC_ERR_INPUT) throw std::runtime_error(rsqc_last_error(gpu));
-            if (rc == RSQC_OK) {
-                if (o.verbosity) for (int k = 0; k < di.n_bad_refid && k < 64; ++k) cerr << "Unrecognized RefID on alignment: " << di.bad_refid[k] << endl;
-                if (di.unsorted && !warned_unsorted) {
-                    cerr << "Warning: The input bam does not appear to be sorted. An unsorted bam will yield incorrect results" << endl;
-                    warned_unsorted = true;
-                }
-            }
-        } else if (device_decode) {
-            // ---- one GPU, device decode: the host reads the file and frames the BGZF blocks, nothing else
-            rsqc_decode_info di{};
-            BgzfFeeder &feed = *feeders[0];
-            rc = decode_range(gpu, feed, decode_params(o, n_ref_bam, 0), first_voff, 0, di, [&](const rsqc_decode_window &w) {
-                bool revisit = false;
-                for (uint32_t k = 0; k < w.n_runs; ++k) {
-                    const int32_t t = w.run_tid[k];
-                    if (t < 0 || (!visit.empty() && visit.back() == t)) continue;
-                    if (std::find(visit.begin(), visit.end(), t) != visit.end()) revisit = true;     // a contig that comes back
-                    visit.push_back(t);
-                    if (o.has_fasta && (size_t)t < in_fasta.size() && !in_fasta[(size_t)t])      // src/RNASeQC.cpp:350-352
-                        cerr << "Warning: Provided Fasta does not contain chromosome " << ann.contig_names[(size_t)t]
-                             << ". No GC statistics will be collected for this chromosome" << endl;
-                }
-                if (revisit && !warned_unsorted) {
-                    cerr << "Warning: The input bam does not appear to be sorted. An unsorted bam will yield incorrect results" << endl;
-                    warned_unsorted = true;
-                }
-                alignmentCount += w.n_records;
-                if (o.verbosity > 1) cout << "Alignments processed: " << alignmentCount << endl;
-            });
-            if (rc == RSQC_ERR_INPUT) throw std::runtime_error(rsqc_last_error(gpu));
-            if (rc == RSQC_OK) {
-                if (o.verbosity) for (int k = 0; k < di.n_bad_refid && k < 64; ++k) cerr << "Unrecognized RefID on alignment: " << di.bad_refid[k] << endl;
-                if (di.unsorted && !warned_unsorted) {
-                    cerr << "Warning: The input bam does not appear to be sorted. An unsorted bam will yield incorrect results" << endl;
-                    warned_unsorted = true;
-                }
-            }
-        } else
-        for (;;) {
-            HostBatch &hb = bufs[cur];
-            hb.clear();
-            hb.file_index_base = alignmentCount;
-            const size_t n = bam.read_batch(hb, BATCH);              // decode overlaps the previous batch on the GPU
-            if (in_flight) { if ((rc = rsqc_wait(gpu)) != RSQC_OK) break; in_flight = false; }
-            if (n == 0) break;
-            // stderr of the reference's loop: the names of records with a RefID the header lacks (src/RNASeQC.cpp:333-337, under -v)
-            // and the sort warning (:354-355).  The reference repeats the warning for every offending record; it is given
-            // once here -- an unsorted file voids the results either way (the static index does not reproduce what the
-            // reference's destructively trimmed window would count).
-            if (o.verbosity) for (auto &nm : hb.bad_refid) cerr << "Unrecognized RefID on alignment: " << nm << endl;
-            bool revisit = false;
-            for (int32_t t : hb.seg_tid) if (t >= 0 && (visit.empty() || visit.back() != t)) {
-                if (std::find(visit.begin(), visit.end(), t) != visit.end()) revisit = true;     // a contig that comes back
-                visit.push_back(t);
-                if (o.has_fasta && (size_t)t < in_fasta.size() && !in_fasta[(size_t)t])      // src/RNASeQC.cpp:350-352
-                    cerr << "Warning: Provided Fasta does not contain chromosome " << ann.contig_names[(size_t)t]
-                         << ". No GC statistics will be collected for this chromosome" << endl;
-            }
-            if ((hb.unsorted || revisit) && !warned_unsorted) {
-                cerr << "Warning: The input bam does not appear to be sorted. An unsorted bam will yield incorrect results" << endl;
-                warned_unsorted = true;
-            }
-            alignmentCount += n;
-            rsqc_batch view = hb.view();
-            if ((rc = rsqc_submit(gpu, &view)) != RSQC_OK) break;
-            in_flight = true;
-            cur ^= 1;
-            if (o.verbosity > 1) cout << "Alignments processed: " << alignmentCount << endl;
-        }
-        rsqc_results res{};
-        if (rc == RSQC_OK && shards.size() > 1) {
-            rc = rsqc_refresh_results(gpu, &res);
-            res.read_length = merged.read_length;
-            res.n_fragment_sizes = (uint32_t)merged.fsize.size(); res.fragment_size = merged.fsize.data(); res.fragment_count = merged.fcount.data();
-            res.fragment_samples_remaining = merged.remaining;
-        } else
-        if (rc == RSQC_OK) rc = rsqc_finalize(gpu, &res);
-        const auto tb1 = std::chrono::steady_clock::now();
-        if (rc == RSQC_ERR_BAD_CIGAR) throw std::invalid_argument("Unrecognized Cigar Op ");
-        if (rc == RSQC_ERR_EMPTY_MEDIAN) throw std::range_error("Cannot compute median of an empty list");
-        if (rc != RSQC_OK) { cerr << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; rsqc_destroy(gpu); return 10; }
-        if (o.verbosity) {
-            const double secs = std::chrono::duration<double>(tb1 - tb0).count();
-            cout << "Time Elapsed: " << secs << "; Alignments processed: " << alignmentCount << endl;
-            if (o.verbosity > 1) cout << "Average Reads/Sec: " << (double)alignmentCount / secs << endl;
-            if (o.verbosity > 1 && sam_input) cout << "(decode: " << (in_fmt == InputFormat::SamBgzf ? "BGZF inflate and SAM text parsing" : "SAM text") << " on the GPU)" << endl;
-            else if (o.verbosity > 1 && device_decode) cout << "(decode: BGZF inflate and record parsing on the GPU)" << endl;
-            else if (o.verbosity > 1 && shards.size() == 1) cout << "(decode threads: " << bam.inflate_threads() << " inflate + " << bam.parse_threads() << " parse)" << endl;
-            cout << "Estimating library complexity..." << endl;
-            cout << "Generating report" << endl;
-        }
-        ReportConfig cfg;
-        cfg.output_dir = out_dir; cfg.sample_name = SAMPLENAME; cfg.sample_given = o.has_sample;
-        cfg.use_rpkm = o.rpkm; cfg.write_coverage = o.coverage; cfg.detection_threshold = (unsigned)o.detection;
-        cfg.filter_tags = o.tags;
-        const auto tr0 = std::chrono::steady_clock::now();
-        write_reports(cfg, ann, res, visit);
-        const auto tr1 = std::chrono::steady_clock::now();
-        rsqc_group_destroy(xgroup);
-        for (auto &sh : shards) rsqc_destroy(sh.gpu);
-        if (o.verbosity > 1) {
-            // where the wall time outside the reference's `Average Reads/Sec` window goes (extension; the window itself is above)
-            auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-            cout << "Wall time: " << sec(t_start, std::chrono::steady_clock::now()) << " s = GTF " << sec(t0, t1)
-                 << " + waiting for the GPU context " << sec(t_gpu0, t_gpu1) << " + index / annotation upload / buffers " << sec(t_gpu1, tb0) - 0.0
-                 << " + BAM loop " << sec(tb0, tb1) << " + reports " << sec(tr0, tr1) << " + release " << sec(tr1, std::chrono::steady_clock::now())
-                 << " (the GPU context and the page-locked feed buffers come up beside the GTF parse)" << endl;
         }
     } catch (Help &) {
         usage(cout);
-        return 4;
+        code = 4;
     } catch (ParseError &e) {
         usage(cerr); cerr << endl << "Argument parsing error: " << e.what() << endl;
-        return 5;
+        code = 5;
     } catch (ValidationError &e) {
         usage(cerr); cerr << endl << "Argument validation error: " << e.what() << endl;
-        return 6;
-    } catch (std::invalid_argument &e) {
-        cerr << "Invalid argument type provided: " << e.what() << endl;
-        return 7;
-    } catch (FileError &e) {
-        cerr << e.what() << endl;
-        return 10;
-    } catch (GtfError &e) {
-        cerr << "Failed to parse the GTF: " << e.what() << endl;
-        return 11;
-    } catch (BedError &e) {
-        cerr << "Failed to parse the BED: " << e.what() << endl;
-        return 11;
-    } catch (std::length_error &e) {
-        cerr << "Unable to parse the GFT lines" << endl << e.what() << endl;
-        return 1;
-    } catch (std::range_error &e) {
-        cerr << "Invalid range" << endl << e.what() << endl;
-        return 2;
-    } catch (std::domain_error &e) {
-        cerr << "Unable to perform string conversion" << endl << e.what() << endl;
-        return 3;
-    } catch (std::bad_alloc &e) {
-        cerr << "Memory allocation failure. Out of memory" << endl << e.what() << endl;
-        return 10;
-    } catch (std::exception &e) {
-        cerr << "Encountered an IO failure" << endl << e.what() << endl;
-        return 10;
+        code = 6;
     } catch (...) {
-        cerr << "Unknown error" << endl;
-        return -1;
+        code = explain_exception("");
     }
-    return 0;
+    // nothing of the process is left on the device: the context was asked for on a thread, which is waited for first
+    try { S.finish_reports(); } catch (...) {}
+    if (S.gpu_ready.valid()) (void)S.gpu_ready.get();
+    if (S.feed_ready.valid()) (void)S.feed_ready.get();
+    if (S.gpu) rsqc_destroy(S.gpu);
+    return code;
 }

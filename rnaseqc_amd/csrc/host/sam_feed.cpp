@@ -129,6 +129,13 @@ SamTextFeeder::~SamTextFeeder() {
 }
 
 bool SamTextFeeder::open(const std::string &path) {
+    // the next file on the same feeder (a cohort): the reader of the file before is stopped first; the chunk buffers stay
+    { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
+    cv_.notify_all();
+    if (th_.joinable()) th_.join();
+    if (fd_ >= 0) { close(fd_); fd_ = -1; }
+    head_.clear();
+    head_i_ = tail_i_ = count_ = 0; lent_ = nullptr; eof_ = false; stop_ = false; error_.clear(); ms_read = 0;
     fd_ = ::open(path.c_str(), O_RDONLY);
     return fd_ >= 0;
 }
@@ -148,9 +155,12 @@ void SamTextFeeder::start(size_t chunk_bytes) {
     chunk_bytes_ = std::max<size_t>(chunk_bytes, head_.size() + 1);
     for (auto &c : ring_) {
         c.cap = chunk_bytes_;
+        if (c.data && c.alloc >= c.cap) continue;                           // (page-locked for a file before this one)
+        if (c.data) { if (c.pinned) rsqc_host_free(c.data); else free(c.data); }
         c.data = (uint8_t *)rsqc_host_alloc(c.cap);
         c.pinned = c.data != nullptr;
         if (!c.data) c.data = (uint8_t *)malloc(c.cap);
+        c.alloc = c.cap;
     }
     th_ = std::thread([this] { producer(); });
 }

@@ -35,12 +35,12 @@ bool read_sam_header(const std::string &path, SamHeader &h);
 // Plain SAM text in page-locked chunks, read sequentially (read(2): a FIFO or /dev/stdin works) by a read-ahead thread.
 class SamTextFeeder {
 public:
-    struct Chunk { uint8_t *data = nullptr; size_t cap = 0, bytes = 0; bool pinned = false; };
+    struct Chunk { uint8_t *data = nullptr; size_t cap = 0, bytes = 0, alloc = 0; bool pinned = false; };   // cap: bytes a chunk holds for this file; alloc: allocated
     SamTextFeeder() = default;
     ~SamTextFeeder();
     SamTextFeeder(const SamTextFeeder &) = delete;
     SamTextFeeder &operator=(const SamTextFeeder &) = delete;
-    bool open(const std::string &path);
+    bool open(const std::string &path);                      // may be called again for the next file: the chunk buffers are kept
     // the first bytes of the input (read and kept: they are the first chunk's); sniffs a stream without losing them
     const std::vector<uint8_t> &peek(size_t n);
     void start(size_t chunk_bytes);

@@ -233,13 +233,11 @@ int rsqc_set_annotation(rsqc_ctx *c, const rsqc_annotation *a, const uint8_t *ow
     if ((rc = dev_alloc(c, c->d_cov, (size_t)(run + 64) * 4, false))) return rc;
     const uint32_t ovf_cap = 1u << 20;
     if ((rc = dev_alloc(c, c->d_ovf_index, (size_t)ovf_cap * 8, false))) return rc;
-    HIP_TRY(c, hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, c->prio_side));
-    HIP_TRY(c, hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, c->prio_side));
-    HIP_TRY(c, hipStreamCreateWithPriority(&c->stream4, hipStreamNonBlocking, c->prio_side));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join3, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join4, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    // (the side streams and their events outlive rsqc_clear_inputs: made for the first annotation, reused by the next)
+    for (hipStream_t *s : {&c->stream2, &c->stream3, &c->stream4})
+        if (!*s) HIP_TRY(c, hipStreamCreateWithPriority(s, hipStreamNonBlocking, c->prio_side));
+    for (hipEvent_t *e : {&c->ev_join3, &c->ev_join4, &c->ev_fork, &c->ev_join})
+        if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     char *A = (char *)c->d_arena.p;
     DevAccum &acc = c->acc;
     acc.gene_reads = (unsigned long long *)(A + c->off_u64);
@@ -360,6 +358,62 @@ int rsqc_reset(rsqc_ctx *c) {
     const int rc = zero_accumulators(c);
     RSQC_TRACE("reset: enqueued");
     return rc;
+}
+
+int rsqc_clear_inputs(rsqc_ctx *c) {
+    if (!c) return RSQC_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // everything in flight: the batches on the main stream, the end-of-file stage's side streams, the decode's copy stream
+    for (hipStream_t s : {c->dec.copy_stream, c->stream, c->stream2, c->stream3, c->stream4})
+        if (s) HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = resolve_events(c)) return rc;
+    if (c->fin_e0) { c->event_pool.push_back(c->fin_e0); c->event_pool.push_back(c->fin_e1); c->fin_e0 = c->fin_e1 = nullptr; }
+    for (auto *u : c->transient) retire_batch(c, u);
+    c->transient.clear();
+    free_parked(c);
+    // an open decode stream is dropped with its carried-over bytes; its window buffers stay
+    c->dec.active = false; c->dec.pending = false; c->dec.tail = 0;
+    // the batches in flight hand their buffers back to the pools; what the pass has emitted so far goes with the arenas
+    for (auto &pb : c->pair_pool) pb.used = false;
+    for (auto &fb : c->frag_pool) fb.used = false;
+    for (auto &gb : c->gc_pool) gb.used = false;
+    c->pairs_in_flight.clear(); c->frags_in_flight.clear(); c->gcs_in_flight.clear();
+    for (Arena *a : {&c->pair_arena, &c->frag_arena, &c->gc_arena}) {
+        for (int k = 0; k < a->n_col; ++k) a->col[k].release();
+        a->used = a->cap = 0;
+    }
+    // the annotation, the BED and the reference, and everything sized from them
+    for (auto &b : c->ann_bufs) b.release();
+    c->ann_bufs.clear();
+    for (DevBuf *b : {&c->d_arena, &c->d_cov, &c->d_ei_rank, &c->d_ovf_index, &c->d_table, &c->d_tab_off, &c->d_tab_cap,
+                      &c->d_ref_bits, &c->d_ref_off, &c->d_ref_len, &c->d_gc_bins, &c->d_exon_gc,
+                      &c->d_rl_summary}) b->release();          // (the per-batch Read-Length summaries, 17 MB: made again by the next pass's first batch)
+    if (c->h_arena) { (void)hipHostFree(c->h_arena); c->h_arena = nullptr; }
+    c->arena_bytes = 0;
+    c->dann = DevAnnotation{}; c->dref = DevReference{};
+    uint32_t *const tile_span = c->acc.tile_span;          // (d_tiles is sized by the batches, not by the annotation: kept)
+    c->acc = DevAccum{}; c->acc.tile_span = tile_span;
+    c->d_ge_off = c->d_ge_row = c->d_gene_cov_off = c->d_gene_coding = c->d_gene_order = nullptr;
+    c->d_gene_flags = c->d_gene_owned = nullptr;
+    c->n_ref = c->n_contigs = c->n_genes = c->n_listed = c->n_exons = 0;
+    c->k3_large = c->k3_medium = c->k3_xlarge = c->k3_le6144 = c->k3_le3072 = c->k3_le2048 = c->k3_le1024 = 0;
+    c->cov_entries = 0; c->n_exons_outside_gene = 0;
+    std::vector<uint32_t>().swap(c->exon_row_id);
+    std::vector<double>().swap(c->h_exon_gc);
+    c->h_gc.clear();
+    c->have_ann = c->have_bed = c->have_ref = false;
+    // the pass that was open, as rsqc_reset leaves it
+    free_sort_scratch(c->gc_scratch); free_sort_scratch(c->frag_scratch);
+    c->h_fsize.clear(); c->h_fcount.clear(); c->frag_remaining = 0; c->frag_kept = 0;
+    c->finalized = false; c->early_copied = false;
+    c->next_record_base = 0; c->name_mode = -1; c->have_ranges = false; c->have_composed_rl = false;
+    c->batch_file_index.clear(); c->batch_records.clear();
+    c->h_rl_offset.clear(); c->h_rl_span.clear(); c->h_rl_state.clear();
+    c->h_sample_file.clear(); c->h_sample_size.clear();
+    c->results = rsqc_results{};
+    c->sticky = 0;
+    c->last_error.clear();
+    return RSQC_OK;
 }
 
 void *rsqc_host_alloc(size_t bytes) {

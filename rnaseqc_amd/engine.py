@@ -44,6 +44,7 @@ def load_library():
         lib.rsqc_release.argtypes = [vp, C.c_int]
         lib.rsqc_finalize.argtypes = [vp, C.POINTER(abi.ResultsStruct)]
         lib.rsqc_reset.argtypes = [vp]
+        lib.rsqc_clear_inputs.argtypes = [vp]
         lib.rsqc_get_timing.argtypes = [vp, C.POINTER(abi.TimingStruct)]
         lib.rsqc_reset_timing.argtypes = [vp]
         lib.rsqc_device_accumulators.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -76,7 +77,7 @@ def load_library():
 
 EXPORTED_SYMBOLS = [
     "rsqc_create", "rsqc_destroy", "rsqc_set_annotation", "rsqc_set_bed", "rsqc_set_reference", "rsqc_submit", "rsqc_wait",
-    "rsqc_upload", "rsqc_submit_resident", "rsqc_release", "rsqc_finalize", "rsqc_reset", "rsqc_get_timing",
+    "rsqc_upload", "rsqc_submit_resident", "rsqc_release", "rsqc_finalize", "rsqc_reset", "rsqc_clear_inputs", "rsqc_get_timing",
     "rsqc_reset_timing", "rsqc_device_accumulators", "rsqc_device_vectors", "rsqc_shard_summary", "rsqc_reduce_peer", "rsqc_reduce_group",
     "rsqc_group_create", "rsqc_group_reduce", "rsqc_group_info", "rsqc_group_destroy", "rsqc_refresh_results", "rsqc_finalize_device", "rsqc_host_alloc", "rsqc_host_free", "rsqc_strerror",
     "rsqc_last_error", "rsqc_counter_name", "rsqc_version", "rsqc_qname_hash", "rsqc_qname_hash2",
@@ -324,6 +325,12 @@ class Engine:
 
     def reset(self):
         self._check(self._l.rsqc_reset(self._h))
+
+    def clear_inputs(self):
+        """rsqc_clear_inputs: waits for what is in flight, then drops annotation, BED and reference (and the open pass): the
+        engine is as after its creation, set_annotation / set_bed / set_reference may be called again."""
+        self._check(self._l.rsqc_clear_inputs(self._h))
+        self._keep = []
 
     def timing(self) -> dict:
         t = abi.TimingStruct()
