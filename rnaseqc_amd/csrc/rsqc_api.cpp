@@ -128,6 +128,7 @@ void rsqc_destroy(rsqc_ctx *c) {
     if (c->ev_join3) (void)hipEventDestroy(c->ev_join3);
     if (c->ev_join4) (void)hipEventDestroy(c->ev_join4);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    if (c->ev_retired) (void)hipEventDestroy(c->ev_retired);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (auto *b : all) b->release();
     for (auto &pr : c->k1_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -236,7 +237,7 @@ int rsqc_set_annotation(rsqc_ctx *c, const rsqc_annotation *a, const uint8_t *ow
     // (the side streams and their events outlive rsqc_clear_inputs: made for the first annotation, reused by the next)
     for (hipStream_t *s : {&c->stream2, &c->stream3, &c->stream4})
         if (!*s) HIP_TRY(c, hipStreamCreateWithPriority(s, hipStreamNonBlocking, c->prio_side));
-    for (hipEvent_t *e : {&c->ev_join3, &c->ev_join4, &c->ev_fork, &c->ev_join})
+    for (hipEvent_t *e : {&c->ev_join3, &c->ev_join4, &c->ev_fork, &c->ev_join, &c->ev_retired})
         if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     char *A = (char *)c->d_arena.p;
     DevAccum &acc = c->acc;

@@ -88,7 +88,13 @@ static int run_finalize_kernels(rsqc_ctx *c, bool early_readback = false) {
         // batches, one per contig of a sharded run): they are retired into the arena first, so that the fragment stage runs ONE pass
         // over one dense list instead of one launch per batch over worst-case chunk tables (26 batches: 2.0 ms of frag_local
         // instead of 1.1).  Costs one wait for the batches' kernels here; a single batch in flight is used in place, uncopied.
-        if (c->pairs_in_flight.size() > 1) { if ((rc = retire_completed(c, true))) return rc; }
+        // (That retire also queues the batches' fragment-size candidates into frag_arena ON THE MAIN STREAM, behind the fork event: K5, which
+        //  runs beside on a stream that waits for the fork only, must wait for `ev_retired` as well -- ADVICE r6.)
+        bool retired_here = false;
+        if (c->pairs_in_flight.size() > 1) {
+            if ((rc = retire_completed(c, true))) return rc;
+            if (c->have_bed) { HIP_TRY(c, hipEventRecord(c->ev_retired, c->stream)); retired_here = true; }
+        }
         uint64_t pair_bound = c->pair_arena.used;
         for (size_t idx : c->pairs_in_flight) pair_bound += c->pair_pool[idx].pairs_bound;
         {
@@ -187,6 +193,7 @@ static int run_finalize_kernels(rsqc_ctx *c, bool early_readback = false) {
             if (c->frag_arena.used && c->frag_arena.used + incoming > c->frag_arena.cap) beside = false;
             hipStream_t ks = beside ? c->stream4 : c->stream;
             if (!beside) HIP_TRY(c, hipStreamSynchronize(c->stream));
+            else if (retired_here) HIP_TRY(c, hipStreamWaitEvent(ks, c->ev_retired, 0));      // the arena copies of the retire above (a few small copies: the overlap with K3 / K4 stays)
             for (size_t k = 0; k < c->frags_in_flight.size(); ++k) {
                 FragBuf &fb = c->frag_pool[c->frags_in_flight[k]];
                 const uint32_t n = *fb.h_count;               // (copied when the batch was submitted; the stream has been synchronised)

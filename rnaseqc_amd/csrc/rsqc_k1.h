@@ -415,10 +415,23 @@ __device__ __forceinline__ void k1e_commit(uint32_t *cov_diff, K1eTables &T, con
 constexpr uint64_t K1E_OVF_LONG = 1ull << 63;
 // One reservation per wave call (the lanes of a call that overflow take consecutive slots): the list has ONE counter, and a returning
 // memory atomic on one address completes at about 88 per microsecond chip-wide (MI355X_MICROARCH.md, "dequeue").
-// `stage` / `stage_n` (classify_long_kernel): the workgroup's LDS buffer in front of the list -- its 36 k entries of the contract workload,
+// `stage` / `ctl` (classify_long_kernel): the workgroup's LDS buffer in front of the list -- its 36 k entries of the contract workload,
 // one memory atomic each, were 0.42 ms of that kernel on their own (call r6b); the workgroup moves its buffer to the list when it retires.
+// The buffer's counter `ctl->n` only ever GROWS, so the reservations [base, base + n) of all calls of the workgroup's four waves are
+// disjoint and tile [0, ctl->n) in the order of their atomics.  A reservation that ends beyond the buffer is not written (its entries go
+// straight to the list) and lowers `ctl->end` to its base: every reservation above the lowest such base F starts at or beyond
+// F + (more than K1E_OVF_STAGE - F), i.e. fails as well, and every one below F fits -- the staged entries are exactly [0, min(n, end)).
+// (A failing call used to subtract its reservation again: between the add and the subtract of two waves a third could be handed a range
+//  that a fourth then received once more, one range was never written, and the flush copied unwritten LDS words to the list -- ADVICE r6;
+//  tests/test_k1_overflow_stage.py runs this function under seeded wave schedules.)
 constexpr uint32_t K1E_OVF_STAGE = 1024;
-__device__ __forceinline__ void k1e_overflow(bool over, uint64_t index, unsigned long long *stage = nullptr, uint32_t *stage_n = nullptr) {
+struct K1eStageCtl {
+    uint32_t n;              // slots handed out (monotone; may pass K1E_OVF_STAGE: at most one entry per record of the batch, below 2^32)
+    uint32_t end;            // base of the lowest reservation that did not fit, K1E_OVF_STAGE while all did
+    __device__ __forceinline__ void init() { n = 0u; end = K1E_OVF_STAGE; }
+    __device__ __forceinline__ uint32_t staged() const { return n < end ? n : end; }       // (final after a workgroup barrier)
+};
+__device__ __forceinline__ void k1e_overflow(bool over, uint64_t index, unsigned long long *stage = nullptr, K1eStageCtl *ctl = nullptr) {
     const uint64_t m = WaveSink::prim(over).m;
     if (m == 0ull) return;
     const int lead = __ffsll((unsigned long long)m) - 1;
@@ -426,11 +439,11 @@ __device__ __forceinline__ void k1e_overflow(bool over, uint64_t index, unsigned
     uint32_t base = 0;
     bool staged = false;
     if (stage) {
-        if (lane_id() == lead) base = atomicAdd(stage_n, n);
+        if (lane_id() == lead) base = atomicAdd(&ctl->n, n);
         base = lane_value(base, lead);
-        staged = base + n <= K1E_OVF_STAGE;                  // (wave-uniform; a full buffer: straight to the list, the counter keeps the overshoot)
+        staged = base <= K1E_OVF_STAGE - n;                  // (wave-uniform, n <= 64; a full buffer: straight to the list, the counter keeps the overshoot)
         if (staged && over) stage[base + mask_rank(m)] = index;
-        if (!staged && lane_id() == lead) atomicAdd(stage_n, 0u - n);
+        if (!staged && lane_id() == lead) atomicMin(&ctl->end, base);
     }
     if (!staged) {
         const DevAccum &acc = k1e_lazy_args()->acc;
@@ -439,6 +452,19 @@ __device__ __forceinline__ void k1e_overflow(bool over, uint64_t index, unsigned
         if (over) {
             const uint32_t slot = base + mask_rank(m);
             if (slot < acc.ovf_cap) acc.ovf_index[slot] = index;
+            else atomicExch(acc.error, RSQC_ERR_CAPACITY);
+        }
+    }
+}
+// the workgroup's staged entries to the list (all lanes of the workgroup, after the barrier behind its last k1e_overflow; `piece`: an LDS word)
+__device__ __forceinline__ void k1e_stage_flush(const DevAccum &acc, const unsigned long long *stage, const K1eStageCtl *ctl, uint32_t *piece) {
+    const uint32_t n_st = ctl->staged();
+    if (n_st != 0u) {
+        if (threadIdx.x == 0) *piece = atomicAdd(acc.ovf_count, n_st);
+        __syncthreads();
+        const uint32_t at = *piece;
+        for (uint32_t j = threadIdx.x; j < n_st; j += blockDim.x) {
+            if (at + j < acc.ovf_cap) acc.ovf_index[at + j] = stage[j];
             else atomicExch(acc.error, RSQC_ERR_CAPACITY);
         }
     }
@@ -869,7 +895,7 @@ __device__ __forceinline__ void k1e_defer(K1eTables &T, uint64_t m, uint32_t idx
 template <bool LANE_CHUNK>
 __device__ __forceinline__ void k1e_long_call(const DevAnnotation &a, const DevParams &p, const DevBatch &b, uint32_t *cov_diff,
                                               const ContigInfo &ci, K1eTables &T, uint32_t idx, bool hq, bool on0, uint32_t &sum_blk,
-                                              const K1ePairDst &held, uint32_t chunk, unsigned long long *stage, uint32_t *stage_n) {
+                                              const K1ePairDst &held, uint32_t chunk, unsigned long long *stage, K1eStageCtl *stage_ctl) {
     const int l = lane_id();
     if (!on0) idx = 0u;
     const int4 cv = ld32(reinterpret_cast<const int4 *>(b.core), idx);
@@ -912,7 +938,7 @@ __device__ __forceinline__ void k1e_long_call(const DevAnnotation &a, const DevP
     const uint32_t qh2 = b.qhash2 ? ld32(b.qhash2, idx) : 0u;
     EiOut eo; bool over = false;
     exon_metrics_ei<FAST_BLOCKS, WaveSink>(a, p, ci, fl, B.bs, B.len, hq, eo, over, cnt, fast, cw.nblocks);
-    k1e_overflow(on && cw.nblocks >= 1 && (over || !fast), (uint64_t)idx, stage, stage_n);
+    k1e_overflow(on && cw.nblocks >= 1 && (over || !fast), (uint64_t)idx, stage, stage_ctl);
     k1e_commit<FAST_BLOCKS, LANE_CHUNK>(cov_diff, T, eo, B.len, fl, qhash, qh2, held, chunk);
     if (k1e_lane_below<RSQC_N_COUNTERS>() && cnt.vec) atomicAdd(&T.cnt32[l], cnt.vec);
 }
@@ -1421,12 +1447,12 @@ __global__ void __launch_bounds__(RSQC_K1_THREADS)              // (103 VGPRs: f
 classify_long_kernel(K1Args A, uint32_t k1_grid) {
     __shared__ K1eTables T;
     __shared__ unsigned long long s_stage[K1E_OVF_STAGE];       // records for the general kernel, moved to its list at the end (k1e_overflow)
-    __shared__ uint32_t s_stage_n;
+    __shared__ K1eStageCtl s_stage_ctl;
     const DevAnnotation &a = A.a; const DevBatch &b = A.b; const DevAccum &acc = A.acc;
     const K1ePairDst held = {(uint64_t)(uintptr_t)acc.pairs, acc.pair_chunk_cap};
     const int l = lane_id();
     T.init(0u);
-    if (threadIdx.x == 0) s_stage_n = 0u;
+    if (threadIdx.x == 0) s_stage_ctl.init();
     __syncthreads();
     uint32_t sum_blk = 0;
     const uint32_t n_rec = (uint32_t)b.n;
@@ -1449,8 +1475,8 @@ classify_long_kernel(K1Args A, uint32_t k1_grid) {
             const ContigInfo ci = (tid >= 0 && tid < a.n_contigs) ? a.contig[tid] : ContigInfo{0, 0, 0, 0, 0, 0, 0, 0};
             // (room for this call's pairs in the workgroup's own chunk even if the three other waves are emitting theirs: 4 x 64 x FAST_SET)
             const bool own = (uint32_t)__builtin_amdgcn_readfirstlane((int)T.pairs) + 4u * 64u * (uint32_t)FAST_SET <= acc.pair_chunk_cap;
-            if (own) k1e_long_call<false>(a, A.p, b, acc.cov_diff, ci, T, idx, hq, mine, sum_blk, held, k1_grid + blockIdx.x, s_stage, &s_stage_n);
-            else k1e_long_call<true>(a, A.p, b, acc.cov_diff, ci, T, idx, hq, mine, sum_blk, held, chunk, s_stage, &s_stage_n);
+            if (own) k1e_long_call<false>(a, A.p, b, acc.cov_diff, ci, T, idx, hq, mine, sum_blk, held, k1_grid + blockIdx.x, s_stage, &s_stage_ctl);
+            else k1e_long_call<true>(a, A.p, b, acc.cov_diff, ci, T, idx, hq, mine, sum_blk, held, chunk, s_stage, &s_stage_ctl);
         }
     }
     {
@@ -1460,16 +1486,7 @@ classify_long_kernel(K1Args A, uint32_t k1_grid) {
     __syncthreads();
     T.flush(0ull);
     if (threadIdx.x == 0) acc.pair_chunk_count[k1_grid + blockIdx.x] = T.pairs < acc.pair_chunk_cap ? T.pairs : acc.pair_chunk_cap;
-    const uint32_t n_st = s_stage_n;                            // (final since the barrier)
-    if (n_st != 0u) {
-        if (threadIdx.x == 0) T.piece = atomicAdd(acc.ovf_count, n_st);
-        __syncthreads();
-        const uint32_t at = T.piece;
-        for (uint32_t j = threadIdx.x; j < n_st; j += blockDim.x) {
-            if (at + j < acc.ovf_cap) acc.ovf_index[at + j] = s_stage[j];
-            else atomicExch(acc.error, RSQC_ERR_CAPACITY);
-        }
-    }
+    k1e_stage_flush(acc, s_stage, &s_stage_ctl, &T.piece);     // (the counter is final since the barrier)
 }
 
 }  // namespace rsqc

@@ -151,3 +151,45 @@ def many_exon_case():
                   wide_index=np.zeros(0, np.uint64), wide_nm=np.zeros(0, np.int32), wide_l_qseq=np.zeros(0, np.int32),
                   wide_n_cigar=np.zeros(0, np.uint32))
     return ann, batch
+
+
+FULL_STAGE_CONTIG_LENGTH = 300_000
+
+
+def full_stage_case(n=12_000):
+    """Every record is deferred and about half of them fill the long kernel's LDS stage.  Four genes stacked on one stretch: two whose
+    single exon spans it (one per strand) and two made of random short exons, so that the intervals lie under two, three or four exons.
+    `n` mates of four 20-base blocks each, 20 bases apart: classify_ei_kernel defers all of them (four blocks), and classify_long_kernel
+    hands those with a block in an interval under more than two exons to the general kernel -- through the 1024-entry stage of its
+    workgroup, which a grid of one to three workgroups fills several times over, in calls of 1 to 64 lanes."""
+    rng = np.random.default_rng(77)
+    span_lo, span_hi = 100, 100 + 20 * n + 2_000
+    assert span_hi < FULL_STAGE_CONTIG_LENGTH
+    rows = []
+    for gid, strand, lo, hi in (("W0", "+", span_lo, span_hi), ("W1", "-", span_lo + 50, span_hi - 50)):
+        rows.append(dict(contig="c", type="gene", start=lo, end=hi, strand=strand, gene_id=gid, gene_name=gid, transcript_type="protein_coding"))
+        rows.append(dict(contig="c", type="exon", start=lo, end=hi, strand=strand, gene_id=gid, exon_id=gid + "_e0", gene_name=gid, transcript_type="protein_coding"))
+    for gid, strand in (("S0", "+"), ("S1", "-")):
+        exons, x = [], span_lo + int(rng.integers(0, 300))
+        while x + 200 < span_hi:
+            ln = int(rng.integers(30, 200))
+            exons.append((x, x + ln))
+            x += ln + int(rng.integers(100, 700))
+        rows.append(dict(contig="c", type="gene", start=exons[0][0], end=exons[-1][1], strand=strand, gene_id=gid, gene_name=gid, transcript_type="protein_coding"))
+        for k, (s, e) in enumerate(exons):
+            rows.append(dict(contig="c", type="exon", start=s, end=e, strand=strand, gene_id=gid, exon_id="%s_e%d" % (gid, k), gene_name=gid, transcript_type="protein_coding"))
+    ann = Annotation.from_rows(["c"], rows)
+    cig = [(M, 20), (N, 5), (M, 20), (N, 5), (M, 20), (N, 7), (M, 20)]
+    recs = []
+    for i in range(n):
+        first = i % 2 == 0
+        recs.append(dict(qname="q%d" % (i // 2), tid=0, pos=300 + 20 * i, cigar=cig, flag=99 if first else 147, mapq=255, nm=0,
+                         mpos=300 + 20 * (i ^ 1), mtid=0, isize=117 if first else -117))
+    return ann, Batch.from_records(recs)
+
+
+def full_stage_bed(n=12_000):
+    """Intervals of 2 500 bases every 6 000 along full_stage_case's stretch: pairs inside them are fragment-size candidates."""
+    from rnaseqc_amd.model import Bed
+    starts = list(range(1_000, 100 + 20 * n, 6_000))
+    return Bed.from_intervals([0] * len(starts), starts, [x + 2_500 for x in starts])

@@ -68,9 +68,43 @@ def build_k1(coarse=True):
     return so
 
 
-def run_k1(params, ann, batch, grid=2, want_cov=False, slow_kernel=True, coarse=True, bed=None):
-    """The per-record KERNELS (rsqc_k1.h) on the 64-lane fiber emulation of wavemu.h, `grid` workgroups of 256 lanes."""
+STAGE_POISON = 0xDEADDEADDEADDEAD
+STAGE_SLOTS = 1024                     # K1E_OVF_STAGE (rsqc_k1.h)
+
+
+def run_overflow_script(start, calls, seed=0, cap=1 << 16):
+    """k1e_overflow + the flush of classify_long_kernel's tail (rsqc_k1.h), one workgroup of four waves under the emulation.
+    start: entries already staged; calls: four lists (one per wave) of 64-bit lane masks, one k1e_overflow call each;
+    seed: wavemu.h's seeded schedule (0: round-robin).  Returns (list entries as a uint64 array, expected entries, (counter, end))."""
+    lib = C.CDLL(build_k1(True))
+    assert len(calls) == 4
+    flat = np.array([m for w in calls for m in w] + [0], np.uint64)
+    n_calls = np.array([len(w) for w in calls], np.uint32)
+    first = np.concatenate([[0], np.cumsum(n_calls)[:-1]]).astype(np.uint32)
+    out = np.zeros(cap, np.uint64); count = C.c_uint32(0); ctl = np.zeros(2, np.uint32)
+    lib.k1emu_set_schedule_seed.argtypes = [C.c_ulonglong]
+    lib.k1emu_overflow_script.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.k1emu_set_schedule_seed(int(seed))
+    try:
+        rc = lib.k1emu_overflow_script(int(start), flat.ctypes.data, first.ctypes.data, n_calls.ctypes.data, STAGE_POISON, out.ctypes.data, cap,
+                                       C.addressof(count), ctl.ctypes.data)
+    finally:
+        lib.k1emu_set_schedule_seed(0)
+    if rc:
+        raise RuntimeError("k1emu_overflow_script rc=%d" % rc)
+    want = [(1 << 48) | j for j in range(start)]
+    for w, masks in enumerate(calls):
+        for c, m in enumerate(masks):
+            want += [(w << 40) | (c << 8) | l for l in range(64) if (int(m) >> l) & 1]
+    return out[:count.value].copy(), np.array(sorted(want), np.uint64), (int(ctl[0]), int(ctl[1]))
+
+
+def run_k1(params, ann, batch, grid=2, want_cov=False, slow_kernel=True, coarse=True, bed=None, seed=0):
+    """The per-record KERNELS (rsqc_k1.h) on the 64-lane fiber emulation of wavemu.h, `grid` workgroups of 256 lanes.
+    seed != 0: wavemu.h's seeded schedule (random wave order, a yield after every atomic) instead of round-robin."""
     lib = C.CDLL(build_k1(coarse))
+    lib.k1emu_set_schedule_seed.argtypes = [C.c_ulonglong]
+    lib.k1emu_set_schedule_seed(int(seed))
     a, b = ann.to_struct(), batch.to_struct()
     o = Out()
     G, E = ann.n_genes_listed, ann.n_exons
@@ -86,6 +120,7 @@ def run_k1(params, ann, batch, grid=2, want_cov=False, slow_kernel=True, coarse=
     rc = lib.k1emu_run_bed(C.byref(params), C.byref(a), C.byref(b), C.byref(bs) if bs is not None else None, C.c_int(grid), C.c_int(1 if slow_kernel else 0),
                            abi.ptr(o.counters), abi.ptr(o.gene_reads), abi.ptr(o.gene_unique), abi.ptr(o.gene_fragments), abi.ptr(o.exon_reads), C.byref(rl),
                            abi.ptr(o.cov) if want_cov else None, abi.ptr(stats))
+    lib.k1emu_set_schedule_seed(0)
     if rc:
         raise RuntimeError("k1emu rc=%d" % rc)
     o.read_length = rl.value

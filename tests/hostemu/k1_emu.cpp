@@ -43,6 +43,42 @@ extern "C" __attribute__((visibility("default"))) unsigned long long k1emu_unifo
 extern "C" __attribute__((visibility("default"))) unsigned long long k1emu_ucache_hits() { return g_k1e_ucache_hits; }
 extern "C" __attribute__((visibility("default"))) unsigned long long k1emu_uniform2_calls() { return g_k1e_uniform2_calls; }
 
+// the seeded schedule of wavemu.h for every kernel this library runs from now on (0: back to the default round-robin)
+extern "C" __attribute__((visibility("default"))) void k1emu_set_schedule_seed(unsigned long long seed) { wavemu::set_seed(seed); }
+
+// k1e_overflow and the flush of classify_long_kernel's tail on their own: ONE workgroup of four waves whose LDS stage already holds `start`
+// entries ((1 << 48) | slot; the rest of the buffer is `poison`).  Wave w makes n_calls[w] calls of k1e_overflow, call c with the lanes of
+// masks[first[w] + c] set and the index (w << 40) | (c << 8) | lane, then the workgroup flushes as the kernel does.  Out: the general
+// kernel's list (ovf_index[0 : *ovf_count], capacity `cap`) and the final stage counter / end.  Returns the kernel error word.
+extern "C" __attribute__((visibility("default")))
+int k1emu_overflow_script(uint32_t start, const uint64_t *masks, const uint32_t *first /*[4]*/, const uint32_t *n_calls /*[4]*/, uint64_t poison,
+                          uint64_t *ovf_index, uint32_t cap, uint32_t *ovf_count, uint32_t *ctl_out /*[2]*/) {
+    static unsigned long long s_stage[K1E_OVF_STAGE];          // (what __shared__ is under the emulation: one workgroup at a time)
+    static K1eStageCtl s_ctl;
+    static uint32_t s_piece;
+    if (start > K1E_OVF_STAGE) return RSQC_ERR_ARG;
+    for (uint32_t j = 0; j < K1E_OVF_STAGE; ++j) s_stage[j] = j < start ? ((1ull << 48) | j) : poison;
+    for (uint32_t j = 0; j < cap; ++j) ovf_index[j] = poison;
+    int error = 0;
+    *ovf_count = 0u;
+    K1Args A{};
+    A.acc.ovf_count = ovf_count; A.acc.ovf_index = ovf_index; A.acc.ovf_cap = cap; A.acc.error = &error;
+    g_k1e_args = &A;
+    wavemu::grid_dim().x = 1; wavemu::block_idx().x = 0;
+    wavemu::run_block(RSQC_K1_THREADS, [&]() {
+        if (threadIdx.x == 0) { s_ctl.init(); s_ctl.n = start; }
+        __syncthreads();
+        const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;
+        for (uint32_t c = 0; c < n_calls[w]; ++c)
+            k1e_overflow(((masks[first[w] + c] >> l) & 1ull) != 0ull, ((uint64_t)w << 40) | ((uint64_t)c << 8) | l, s_stage, &s_ctl);
+        __syncthreads();
+        k1e_stage_flush(A.acc, s_stage, &s_ctl, &s_piece);
+    });
+    g_k1e_args = nullptr;
+    ctl_out[0] = s_ctl.n; ctl_out[1] = s_ctl.end;
+    return error;
+}
+
 // returns 0, an RSQC_ERR_* code, or 1000 + k for a failed internal check k
 extern "C" __attribute__((visibility("default")))
 int k1emu_run_bed(const rsqc_params *p, const rsqc_annotation *a, const rsqc_batch *b, const rsqc_bed *bed, int grid, int slow_kernel,

@@ -7,6 +7,12 @@
 // against the oracle in the GPU-less build container.  A collective (ballot / shuffle / barrier) parks the calling lane
 // until every lane of its wave (workgroup) has arrived; lanes of a wave must therefore reach the same collectives --
 // which is what the hardware requires of converged code as well.  Atomics are plain read-modify-writes (one thread).
+//
+// Schedule.  By default the lanes run round-robin and change only at collectives: the waves of a workgroup then pass through
+// their atomics in one fixed order.  wavemu::set_seed(s != 0) switches to a SEEDED schedule: the scheduler picks the next
+// wave pseudo-randomly (every unfinished lane of that wave gets one turn), and a lane also yields after every LDS / memory
+// atomic -- so that the read-modify-write sequences of different waves on one counter interleave in an order that the seed
+// decides and repeats.  set_seed(0): the default schedule, bit for bit.
 #pragma once
 #define RSQC_WAVE_EMU 1
 
@@ -50,7 +56,11 @@ struct Block {
     std::function<void()> body;
 };
 inline Block *&cur_block() { static Block *b = nullptr; return b; }
+inline uint64_t &sched_state() { static uint64_t s = 0; return s; }              // 0: round-robin (the default)
+inline void set_seed(uint64_t seed) { sched_state() = seed ? (seed * 0x9E3779B97F4A7C15ull) | 1ull : 0ull; }
+inline uint64_t sched_next() { uint64_t &x = sched_state(); x ^= x >> 12; x ^= x << 25; x ^= x >> 27; return (x * 0x2545F4914F6CDD1Dull) >> 33; }   // (xorshift64*)
 inline void yield() { Block *b = cur_block(); swapcontext(&b->lanes[(size_t)b->cur].ctx, &b->sched); }
+inline void atomic_done() { if (sched_state() && cur_block()) yield(); }          // seeded schedule: another wave may run between two atomics
 inline int tid() { return cur_block()->cur; }
 inline WaveState &wave() { Block *b = cur_block(); return b->waves[(size_t)(b->cur / kWave)]; }
 inline int lanes_in_wave() { Block *b = cur_block(); const int w = b->cur / kWave; const int left = b->n_threads - w * kWave; return left < kWave ? left : kWave; }
@@ -88,6 +98,23 @@ inline void run_block(int n_threads, const std::function<void()> &body) {
         L.ctx.uc_stack.ss_sp = L.stack; L.ctx.uc_stack.ss_size = kStack; L.ctx.uc_link = &blk.sched;
         makecontext(&L.ctx, (void (*)())fiber_main, 0);
     }
+    if (sched_state()) {
+        const int n_waves = (int)blk.waves.size();
+        std::vector<int> left((size_t)n_waves, 0), live;        // unfinished lanes per wave; the waves that have some
+        for (int t = 0; t < n_threads; ++t) ++left[(size_t)(t / kWave)];
+        for (;;) {
+            live.clear();
+            for (int w = 0; w < n_waves; ++w) if (left[(size_t)w]) live.push_back(w);
+            if (live.empty()) break;
+            const int w = live[(size_t)(sched_next() % live.size())];
+            for (int t = w * kWave; t < n_threads && t < (w + 1) * kWave; ++t) {
+                if (blk.lanes[(size_t)t].done) continue;
+                blk.cur = t;
+                swapcontext(&blk.sched, &blk.lanes[(size_t)t].ctx);
+                if (blk.lanes[(size_t)t].done) --left[(size_t)w];
+            }
+        }
+    } else
     for (;;) {
         bool any = false;
         for (int t = 0; t < n_threads; ++t) {
@@ -154,16 +181,16 @@ inline uint32_t wavemu_mbcnt_hi(uint32_t m, uint32_t add) { const int l = wavemu
 inline int __popcll(unsigned long long x) { return __builtin_popcountll(x); }
 inline int __ffsll(unsigned long long x) { return __builtin_ffsll((long long)x); }
 
-// ---- atomics (one OS thread: plain read-modify-write) ---------------------------------------------------------------
-template <class T> inline T wavemu_add(T *p, T v) { const T o = *p; *p = o + v; return o; }
+// ---- atomics (one OS thread: plain read-modify-write; under a seeded schedule the lane then yields) -----------------------
+template <class T> inline T wavemu_add(T *p, T v) { const T o = *p; *p = o + v; wavemu::atomic_done(); return o; }
 inline uint32_t atomicAdd(uint32_t *p, uint32_t v) { return wavemu_add(p, v); }
 inline int atomicAdd(int *p, int v) { return wavemu_add(p, v); }
 inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { return wavemu_add(p, v); }
 inline double atomicAdd(double *p, double v) { return wavemu_add(p, v); }
-inline uint32_t atomicCAS(uint32_t *p, uint32_t cmp, uint32_t v) { const uint32_t o = *p; if (o == cmp) *p = v; return o; }
-inline uint32_t atomicMax(uint32_t *p, uint32_t v) { const uint32_t o = *p; if (v > o) *p = v; return o; }
-inline uint32_t atomicMin(uint32_t *p, uint32_t v) { const uint32_t o = *p; if (v < o) *p = v; return o; }
-inline int atomicExch(int *p, int v) { const int o = *p; *p = v; return o; }
-inline uint32_t atomicExch(uint32_t *p, uint32_t v) { const uint32_t o = *p; *p = v; return o; }
-inline unsigned long long atomicCAS(unsigned long long *p, unsigned long long cmp, unsigned long long v) { const unsigned long long o = *p; if (o == cmp) *p = v; return o; }
-inline unsigned long long atomicExch(unsigned long long *p, unsigned long long v) { const unsigned long long o = *p; *p = v; return o; }
+inline uint32_t atomicCAS(uint32_t *p, uint32_t cmp, uint32_t v) { const uint32_t o = *p; if (o == cmp) *p = v; wavemu::atomic_done(); return o; }
+inline uint32_t atomicMax(uint32_t *p, uint32_t v) { const uint32_t o = *p; if (v > o) *p = v; wavemu::atomic_done(); return o; }
+inline uint32_t atomicMin(uint32_t *p, uint32_t v) { const uint32_t o = *p; if (v < o) *p = v; wavemu::atomic_done(); return o; }
+inline int atomicExch(int *p, int v) { const int o = *p; *p = v; wavemu::atomic_done(); return o; }
+inline uint32_t atomicExch(uint32_t *p, uint32_t v) { const uint32_t o = *p; *p = v; wavemu::atomic_done(); return o; }
+inline unsigned long long atomicCAS(unsigned long long *p, unsigned long long cmp, unsigned long long v) { const unsigned long long o = *p; if (o == cmp) *p = v; wavemu::atomic_done(); return o; }
+inline unsigned long long atomicExch(unsigned long long *p, unsigned long long v) { const unsigned long long o = *p; *p = v; wavemu::atomic_done(); return o; }
