@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define RSQC_ABI_VERSION 5
+#define RSQC_ABI_VERSION 6
 
 #if defined(__GNUC__)
 #define RSQC_API __attribute__((visibility("default")))
@@ -601,6 +601,35 @@ RSQC_API int rsqc_decode_end(rsqc_ctx *ctx, rsqc_decode_info *out);
  * of judged records with RefID -1).                                                                                         */
 RSQC_API int rsqc_decode_begin_sam(rsqc_ctx *ctx, const rsqc_decode_params *p, const char *const *ref_names);
 RSQC_API int rsqc_decode_submit_text(rsqc_ctx *ctx, const void *text, uint64_t bytes, rsqc_decode_window *out);
+
+/* ---- input in any order (ABI 6) ----------------------------------------------------------------------------------
+ * Every rule of the per-read path assumes a coordinate-sorted file.  Between rsqc_sort_begin and rsqc_sort_end the context COLLECTS
+ * instead: every record that reaches it -- through rsqc_submit, rsqc_submit_resident, rsqc_decode_submit or
+ * rsqc_decode_submit_text -- is appended to a device-resident collection (a stream-ordered device copy: the decode paths' window
+ * buffers and the caller's arrays are free again under the usual rules) and no per-read kernel runs.  Batches may arrive in any
+ * order, file_index_base is ignored, a batch with seg_file_index is RSQC_ERR_ARG, the qhash2 all-or-none rule holds as ever.
+ * rsqc_sort_begin: after the inputs are set and before the pass's first submit (RSQC_ERR_ARG behind one).
+ * rsqc_sort_end (behind rsqc_decode_end, if a decode stream fed the collection): orders the collection STABLY by (tid as unsigned 32
+ * bits, pos as signed) -- unplaced records (tid -1) last, ties in arrival order -- with a radix sort on the device, forms ordinary
+ * batches of at most RSQC_SORT_BATCH records (environment; default 2 097 152) and runs them in order as rsqc_submit_resident would;
+ * a record's file index is its rank in that order.  The context is then in the state those submits leave: rsqc_finalize,
+ * rsqc_reset, rsqc_shard_summary and rsqc_get_timing behave as ever.  rsqc_reset and rsqc_clear_inputs also leave the collecting
+ * mode and free the collection.  The whole input is resident: 44 bytes per record and 4 per CIGAR operation collected -- in columns
+ * that grow by doubling, so up to twice that is allocated, and three times what has been collected while a column is being grown
+ * (the old one goes as soon as its copy is through) -- and 16 more per record while sorting; batches uploaded by rsqc_submit stay
+ * on the device until rsqc_wait, as ever.  A collection the device cannot hold (or of 2^32 - 16 records and more) is
+ * RSQC_ERR_CAPACITY with the sizes in rsqc_last_error -- never a partial result: a batch lost while collecting (capacity, a HIP
+ * error) and any failure of rsqc_sort_end void the pass, every later call returns that code until rsqc_reset; a batch REFUSED with
+ * RSQC_ERR_ARG leaves the collection as it was.  rsqc_finalize between the two calls is RSQC_ERR_ARG.                              */
+typedef struct rsqc_sort_info {
+    uint64_t records;                  /* collected and run                                                          */
+    uint64_t batches_in, batches_out;  /* non-empty batches collected; batches the per-read kernels were given       */
+    uint64_t moved;                    /* records whose rank differs from their arrival index                         */
+    double   key_ms, sort_ms, gather_ms;   /* the reduction over the keys with its read-back; the radix passes; forming the output batches */
+    int32_t  was_sorted;               /* the collection was in order already: no radix pass ran                      */
+} rsqc_sort_info;
+RSQC_API int rsqc_sort_begin(rsqc_ctx *ctx);
+RSQC_API int rsqc_sort_end(rsqc_ctx *ctx, rsqc_sort_info *out);
 
 RSQC_API const char *rsqc_strerror(int code);
 RSQC_API const char *rsqc_last_error(rsqc_ctx *ctx);

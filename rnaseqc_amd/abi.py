@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import numpy as np
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # error codes
 OK, ERR_ARG, ERR_HIP, ERR_BAD_CIGAR, ERR_CAPACITY, ERR_NO_DEVICE, ERR_EMPTY_MEDIAN, ERR_INPUT = 0, -1, -2, -3, -4, -5, -6, -7
@@ -183,6 +183,11 @@ class TimingStruct(C.Structure):
         ("finalize_ms", C.c_double), ("h2d_ms", C.c_double), ("slow_records", C.c_uint64), ("fragment_sizes_ms", C.c_double),
         ("classify_long_ms", C.c_double),
     ]
+
+
+class SortInfo(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("batches_in", C.c_uint64), ("batches_out", C.c_uint64), ("moved", C.c_uint64),
+                ("key_ms", C.c_double), ("sort_ms", C.c_double), ("gather_ms", C.c_double), ("was_sorted", C.c_int32)]
 
 
 def ptr(a: np.ndarray | None):

@@ -52,6 +52,7 @@ struct Options {
     std::vector<std::string> tags;
     int gpus = 0;                      // --gpus (extension): GPUs to shard the BAM over by contig; 0 = RSQC_GPUS or 1
     std::string bam_list; bool has_bam_list = false;   // --bam-list (extension): a cohort, the positionals are `gtf output`
+    bool sort = false;                 // --sort (extension): input in any order, put in coordinate order on the GPU (rsqc_sort_begin / rsqc_sort_end)
 };
 
 void usage(std::ostream &o) {
@@ -83,7 +84,8 @@ void usage(std::ostream &o) {
          "      --coverage-mask=[SIZE]            Bases masked at both transcript ends. Default: 500bp\n"
          "      -d[threshold], --detection-threshold=[threshold]  Counts to call a gene detected. Default: 5 reads\n"
          "      --gpus=[N]                        (extension) Shard the BAM by contig over N GPUs of this node; needs [bam].bai. Default: 1\n"
-         "      --bam-list=[FILE]                 (extension) A cohort on one GPU: FILE lists one input per line, path[<TAB>sample]; the positionals are [gtf] [output]\n";
+         "      --bam-list=[FILE]                 (extension) A cohort on one GPU: FILE lists one input per line, path[<TAB>sample]; the positionals are [gtf] [output]\n"
+         "      --sort                            (extension) Accept input in any order: the records are put in coordinate order on the GPU before they are counted\n";
 }
 
 long to_long(const std::string &flag, const std::string &v) {
@@ -162,6 +164,7 @@ Options parse(int argc, char **argv) {
         else if (name == "coverage") o.coverage = true;
         else if (name == "gpus") o.gpus = (int)to_ulong(name, need());
         else if (name == "bam-list") { o.bam_list = need(); o.has_bam_list = true; }
+        else if (name == "sort") o.sort = true;
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
         else if (name == "detection-threshold") o.detection = to_ulong(name, need());
         else throw ParseError("Flag could not be matched: " + name);
@@ -698,11 +701,11 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     std::vector<int> visit;
     unsigned long long alignmentCount = 0;
     bool warned_unsorted = false;
-    auto warn_unsorted = [&] { if (!warned_unsorted) { cerr << S.prefix << kUnsortedWarning << endl; warned_unsorted = true; } };
+    auto warn_unsorted = [&] { if (!warned_unsorted && !o.sort) { cerr << S.prefix << kUnsortedWarning << endl; warned_unsorted = true; } };
     // a contig the input visits: the order of coverage.tsv, the sort check, the FASTA's gaps (src/RNASeQC.cpp:350-355)
     auto visit_contig = [&](int32_t t, bool &revisit) {
         if (t < 0 || (!visit.empty() && visit.back() == t)) return;
-        if (std::find(visit.begin(), visit.end(), t) != visit.end()) revisit = true;     // a contig that comes back
+        if (std::find(visit.begin(), visit.end(), t) != visit.end()) { revisit = true; if (o.sort) return; }     // a contig that comes back (--sort: expected, listed once)
         visit.push_back(t);
         if (o.has_fasta && (size_t)t < S.in_fasta.size() && !S.in_fasta[(size_t)t])
             cerr << S.prefix << "Warning: Provided Fasta does not contain chromosome " << ann.contig_names[(size_t)t]
@@ -729,6 +732,8 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     S.dirty = true;
     S.t_loop0 = Clock::now();
     rc = RSQC_OK;
+    // --sort: the loops below collect (no per-read kernel runs); rsqc_sort_end orders the records and runs them
+    if (o.sort && (rc = rsqc_sort_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     if (sam_input) {
         // ---- SAM text: the host reads the file (plain) or frames its BGZF blocks, the device does the rest
         rsqc_decode_info di{};
@@ -806,6 +811,16 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
             cur ^= 1;
             if (o.verbosity > 1) cout << "Alignments processed: " << alignmentCount << endl;
         }
+    }
+    rsqc_sort_info sort_info{};
+    if (o.sort && rc == RSQC_OK && (rc = rsqc_sort_end(gpu, &sort_info)) == RSQC_OK) {
+        // the contigs in the order the SORTED records visit them: tid as unsigned, each once (the order of coverage.tsv)
+        std::sort(visit.begin(), visit.end(), [](int a, int b) { return (uint32_t)a < (uint32_t)b; });
+        visit.erase(std::unique(visit.begin(), visit.end()), visit.end());
+        if (o.verbosity)
+            cout << "Sorted on the GPU: records " << sort_info.records << ", batches in " << sort_info.batches_in << ", batches out " << sort_info.batches_out
+                 << ", moved " << sort_info.moved << ", key_ms " << sort_info.key_ms << ", sort_ms " << sort_info.sort_ms << ", gather_ms " << sort_info.gather_ms
+                 << ", was_sorted " << sort_info.was_sorted << endl;
     }
     rsqc_results res{};
     if (rc == RSQC_OK) rc = rsqc_finalize(gpu, &res);
@@ -1117,6 +1132,13 @@ int main(int argc, char **argv) {
             if (o.stranded == "RF" || o.stranded == "rf") strand = RSQC_STRAND_REVERSE;
             else if (o.stranded == "FR" || o.stranded == "fr") strand = RSQC_STRAND_FORWARD;
             else throw ValidationError("--stranded argument must be in {'RF', 'rf', 'FR', 'fr'}");
+        }
+        if (o.sort) {
+            // the sort sits in front of ONE context's ordinary submits: contig sharding needs the index of a sorted file, cohorts are not collected
+            if (o.has_bam_list) throw ValidationError("--sort takes one input (it cannot be combined with --bam-list)");
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--sort runs on one GPU (--gpus, RSQC_GPUS and RSQC_GPU_LIST shard a coordinate-sorted, indexed BAM)");
         }
         // a cohort: the list is read and checked before anything else is touched
         std::vector<Sample> samples;

@@ -116,6 +116,7 @@ void rsqc_destroy(rsqc_ctx *c) {
         if (D.copy_stream) (void)hipStreamDestroy(D.copy_stream);
         for (auto &e : D.pe) if (e) (void)hipEventDestroy(e);
     }
+    sort_drop(c);
     for (auto &b : c->parked) b.release();
     free_sort_scratch(c->gc_scratch); free_sort_scratch(c->frag_scratch);
     c->d_ref_bits.release(); c->d_ref_off.release(); c->d_ref_len.release(); c->d_gc_bins.release(); c->d_exon_gc.release();
@@ -356,6 +357,7 @@ int rsqc_reset(rsqc_ctx *c) {
     if (!c || !c->have_ann) return RSQC_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     RSQC_TRACE("reset: enter");
+    if (c->sort.active || c->sort.core.p) sort_drop(c);
     const int rc = zero_accumulators(c);
     RSQC_TRACE("reset: enqueued");
     return rc;
@@ -372,6 +374,7 @@ int rsqc_clear_inputs(rsqc_ctx *c) {
     for (auto *u : c->transient) retire_batch(c, u);
     c->transient.clear();
     free_parked(c);
+    sort_drop(c);
     // an open decode stream is dropped with its carried-over bytes; its window buffers stay
     c->dec.active = false; c->dec.pending = false; c->dec.tail = 0;
     // the batches in flight hand their buffers back to the pools; what the pass has emitted so far goes with the arenas

@@ -128,6 +128,14 @@ struct DecodeState {
     std::vector<int32_t> sam_last_runs;  // rsqc_decode_end: runs of the last window and of the one that ended the last line
 };
 
+// --sort (rsqc_sort_begin / rsqc_sort_end, rsqc_sort_api.cpp): what has been collected, columns that grow by doubling
+struct SortState {
+    bool active = false;
+    uint64_t n = 0, n_ops = 0, n_wide = 0, cap_n = 0, cap_ops = 0, cap_wide = 0, batches_in = 0;
+    DevBuf core, aux, qh2, key, cigar, wide_index, wide_nm, wide_lq, wide_nc;
+    std::vector<uint64_t> batch_rec0, batch_pool0;   // first record / first operation of every collected batch
+};
+
 }  // namespace rsqc
 using namespace rsqc;            // (every unit that sees this header is host code of the library)
 
@@ -219,6 +227,7 @@ struct rsqc_ctx {
     rsqc_timing timing{};
 
     DecodeState dec;
+    SortState sort;
 
     // host results
     std::vector<uint64_t> h_fcount;
@@ -250,6 +259,9 @@ void free_parked(rsqc_ctx *c);                 // caller: the stream has been sy
 int retire_completed(rsqc_ctx *c, bool all);
 int run_batch(rsqc_ctx *c, UploadedBatch *u);
 const char *device_error_text(int err);
+// collecting mode: the batch's records are appended to the collection instead of being run (rsqc_sort_api.cpp)
+int sort_append(rsqc_ctx *c, UploadedBatch *u);
+void sort_drop(rsqc_ctx *c);                   // leaves the collecting mode and frees the collection (hipFree waits for the device)
 
 template <class T>
 int upload(rsqc_ctx *c, std::vector<DevBuf> &owner, const T *host, size_t n, const T **out, bool from_pool = false) {

@@ -288,6 +288,7 @@ static void finish_finalize_bookkeeping(rsqc_ctx *c) {
 int rsqc_finalize(rsqc_ctx *c, rsqc_results *out) {
     if (!c || !out || !c->have_ann) return RSQC_ERR_ARG;
     if (c->sticky) return c->sticky;
+    if (c->sort.active) return fail(c, RSQC_ERR_ARG, "rsqc_sort_end must precede rsqc_finalize (a collection of rsqc_sort_begin is open)");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
     if (!c->finalized) {
@@ -306,6 +307,7 @@ int rsqc_finalize(rsqc_ctx *c, rsqc_results *out) {
 int rsqc_finalize_device(rsqc_ctx *c) {
     if (!c || !c->have_ann) return RSQC_ERR_ARG;
     if (c->sticky) return c->sticky;
+    if (c->sort.active) return fail(c, RSQC_ERR_ARG, "rsqc_sort_end must precede rsqc_finalize_device (a collection of rsqc_sort_begin is open)");
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->finalized) return RSQC_OK;
     int rc;

@@ -246,6 +246,7 @@ int run_batch(rsqc_ctx *c, UploadedBatch *u) {
         else if (c->name_mode != mode)
             return fail(c, RSQC_ERR_ARG, "rsqc_batch.qhash2 must be given for every batch of a pass or for none (the name identity is 96 or 64 bits for the whole pass)");
     }
+    if (c->sort.active) return sort_append(c, u);   // rsqc_sort_begin: collected now, run by rsqc_sort_end
     const uint64_t tiles = (u->n + RSQC_K1_THREADS - 1) / RSQC_K1_THREADS;
     const uint64_t wave_tiles = (u->n + 63) / 64 + 64;
     if (wave_tiles > c->tile_cap) {

@@ -71,6 +71,8 @@ def load_library():
         lib.rsqc_decode_end.argtypes = [vp, C.POINTER(abi.DecodeInfo)]
         lib.rsqc_decode_begin_sam.argtypes = [vp, C.POINTER(abi.DecodeParams), C.POINTER(C.c_char_p)]
         lib.rsqc_decode_submit_text.argtypes = [vp, vp, C.c_uint64, C.POINTER(abi.DecodeWindow)]
+        lib.rsqc_sort_begin.argtypes = [vp]
+        lib.rsqc_sort_end.argtypes = [vp, C.POINTER(abi.SortInfo)]
         _lib = lib
     return _lib
 
@@ -82,6 +84,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_group_create", "rsqc_group_reduce", "rsqc_group_info", "rsqc_group_destroy", "rsqc_refresh_results", "rsqc_finalize_device", "rsqc_host_alloc", "rsqc_host_free", "rsqc_strerror",
     "rsqc_last_error", "rsqc_counter_name", "rsqc_version", "rsqc_qname_hash", "rsqc_qname_hash2",
     "rsqc_decode_begin", "rsqc_decode_submit", "rsqc_decode_end", "rsqc_decode_begin_sam", "rsqc_decode_submit_text",
+    "rsqc_sort_begin", "rsqc_sort_end",
 ]
 
 
@@ -225,6 +228,17 @@ class Engine:
             names = [arr[k].decode() for k in range(min(info.n_bad_refid, 64))]
         self._check(rc)
         return int(info.records), bool(info.unsorted), int(info.n_bad_refid), names
+
+    # ---- input in any order (rsqc_sort_*) ------------------------------------------------------------------------
+    def sort_begin(self):
+        """Collecting mode: every submit / decode_submit from here on appends to a device-resident collection."""
+        self._check(self._l.rsqc_sort_begin(self._h))
+
+    def sort_end(self) -> dict:
+        """Orders the collection on the device and runs it as ordinary batches; the fields of rsqc_sort_info."""
+        info = abi.SortInfo()
+        self._check(self._l.rsqc_sort_end(self._h, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in abi.SortInfo._fields_}
 
     def read_device(self, ptr, count, dtype):
         """count items of dtype from a device pointer of this context (tests): hipMemcpy of the HIP runtime the library itself is
