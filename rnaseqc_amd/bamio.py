@@ -11,9 +11,13 @@ import numpy as np
 from . import abi
 
 
-def _bgzf_block(data: bytes, level: int = 1) -> bytes:
-    comp = zlib.compressobj(level, zlib.DEFLATED, -15)
-    c = comp.compress(data) + comp.flush()
+def _bgzf_block(data: bytes, level: int = 1, compress=None) -> bytes:
+    """compress: optional callable bytes -> raw DEFLATE stream of them (the tests' hand-built streams); default: zlib at `level`."""
+    if compress is not None:
+        c = compress(data)
+    else:
+        comp = zlib.compressobj(level, zlib.DEFLATED, -15)
+        c = comp.compress(data) + comp.flush()
     bsize = len(c) + 25
     return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize) + c +
             struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
@@ -22,8 +26,9 @@ def _bgzf_block(data: bytes, level: int = 1) -> bytes:
 _EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
-def write_bam(path, contigs, batch, qnames=None, filter_tag="XF", ch_tag="ch", level=1, extra_aux=None):
+def write_bam(path, contigs, batch, qnames=None, filter_tag="XF", ch_tag="ch", level=1, extra_aux=None, compress=None):
     """contigs: [(name, length)]; batch: model.Batch (file order).  qnames: list of bytes or None (uses batch.qname).
+    compress: optional callable that deflates a block's bytes instead of zlib (see _bgzf_block).
     extra_aux: optional callable i -> (bytes before, bytes after) of further aux fields around the standard ones."""
     n = batch.n
     tid = batch.tid_per_record()
@@ -71,7 +76,7 @@ def write_bam(path, contigs, batch, qnames=None, filter_tag="XF", ch_tag="ch", l
         # the header may exceed one block
         for c in chunks:
             for o in range(0, len(c), 60000):
-                f.write(_bgzf_block(c[o:o + 60000], level))
+                f.write(_bgzf_block(c[o:o + 60000], level, compress))
         f.write(_EOF)
 
 
@@ -100,7 +105,7 @@ def sam_consistent(batch):
 _CIGAR_CH = "MIDNSHP=X"
 
 
-def write_sam(path, contigs, batch, qnames=None, ch_tag="ch", filter_tag="XF", bgzf=False, extra_aux=None, level=1):
+def write_sam(path, contigs, batch, qnames=None, ch_tag="ch", filter_tag="XF", bgzf=False, extra_aux=None, level=1, compress=None):
     """The records of write_bam (same names, flags, mates, tags) as SAM text; bgzf=True: BGZF-compressed SAM.
     SEQ is all 'A' (or '*' when empty), QUAL '*'.  CIGAR query lengths must equal l_qseq (sam_consistent).
     extra_aux: optional callable i -> (text before, text after) of further optional fields ("TG:T:value" joined by tabs)."""
@@ -141,7 +146,7 @@ def write_sam(path, contigs, batch, qnames=None, ch_tag="ch", filter_tag="XF", b
     with open(path, "wb") as f:
         if bgzf:
             for o in range(0, len(text), 65280):
-                f.write(_bgzf_block(text[o:o + 65280], level))
+                f.write(_bgzf_block(text[o:o + 65280], level, compress))
             f.write(_EOF)
         else:
             f.write(text)

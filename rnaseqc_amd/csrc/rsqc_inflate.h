@@ -374,8 +374,35 @@ struct InflateOut {
 __device__ __forceinline__ uint32_t inflate_lane_down(uint32_t v, uint32_t delta) { return (uint32_t)__shfl_down((int)v, delta, 64); }
 #endif
 
+// Counters of the host build with -DINF_STATS (tests/test_inflate_crafted.py reads them to prove that a crafted stream reached the
+// path it is named for); the device build and the plain host build compile INF_STAT(x) to nothing.
+#if defined(INF_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+struct InflateStats {
+    unsigned long long near_matches, far_matches, match_bytes, rounds, round_symbols, slow_symbols, dist_hist[16], far_len_hist[10];
+    unsigned long long long_ll[16], long_d[16];          // codes the fast tables do not hold, by code length (inflate_one_symbol, inflate_long_code_here)
+    unsigned long long cuts, cut_lanes;                  // rounds cut at INF_ROUND_BYTES; bit c: a cut at lane c
+    unsigned long long stops_other, stop_lanes;          // walks that ended on INF_K_OTHER; bit k: at lane k
+    unsigned long long past_avail;                       // ... of which: a symbol of the fast tables that runs past the buffered bits
+    unsigned long long max_symbol_bits;                  // the longest symbol (code + extra + code + extra) a walk took
+    unsigned long long one_pass, one_pass_dep, one_pass_far;   // rounds committed in one pass; rounds <= 64 bytes refused (a match reads the round's own output); one-pass rounds with a far source
+    unsigned long long overlap_recip, overlap_sub;       // overlapping copies: dist < 64 (reciprocal table), 64 <= dist < len (conditional subtractions)
+    unsigned long long blocks[3];                        // stored, fixed, dynamic
+    unsigned long long empty_dist_after_full;            // a block with no distance code directly behind one whose distance code was complete
+    unsigned long long full_flushes, last_flush;         // flushes of INF_FLUSH bytes; size of the most recent flush
+    unsigned long long far_min_slack;                    // min over far sources of (flushed bytes - the source's end)
+    unsigned long long max_round_symbols, max_round_matches;
+    unsigned long long one_pass_matches, one_pass_far_matches;   // matches committed by one-pass rounds (they do not go through inflate_copy), and the far ones among them
+    unsigned long long long_here_lanes;                  // bit k: the walk stood on a code the fast table does not hold at lane k (inflate_long_code_here)
+};
+inline InflateStats &inflate_stats() { static InflateStats st{}; return st; }
+#define INF_STAT(x) (x)
+#else
+#define INF_STAT(x) ((void)0)
+#endif
+
 // writes ring bytes [flushed, flushed + n) to the stream and runs them through the CRC; n <= INF_FLUSH
 RSQC_INF_FN void inflate_flush(InflateScratch &S, InflateOut &o, uint32_t n) {
+    INF_STAT(inflate_stats().full_flushes += n == INF_FLUSH ? 1 : 0); INF_STAT(inflate_stats().last_flush = n);
     for (uint32_t j = INF_LANE; j < n; j += INF_W) o.dst[o.flushed + j] = S.ring[(o.flushed + j) & INF_RMASK];
     // lane l: raw register of piece l of INF_W equal pieces; the chunk is right-aligned in them (leading zero bytes leave a
     // register that started from 0 at 0)
@@ -422,27 +449,24 @@ RSQC_INF_FN void inflate_flush(InflateScratch &S, InflateOut &o, uint32_t n) {
 // pos - dist + 258 < pos - INF_RING + 516 <= pos - INF_FLUSH - INF_ROUND_BYTES.
 // The loads follow the flush's stores of the same wave: a workgroup-scope fence (a wait for the stores, the CU's vector
 // cache is coherent within a workgroup) orders them.
-#if defined(INF_STATS) && !defined(__HIP_DEVICE_COMPILE__)
-struct InflateStats { unsigned long long near_matches, far_matches, match_bytes, rounds, round_symbols, slow_symbols, dist_hist[16], far_len_hist[10]; };
-inline InflateStats &inflate_stats() { static InflateStats st{}; return st; }
-#define INF_STAT(x) (x)
-#else
-#define INF_STAT(x) ((void)0)
-#endif
 RSQC_INF_FN void inflate_copy(InflateScratch &S, const InflateOut &o, uint32_t pos, uint32_t dist, uint32_t len) {
-    INF_STAT((dist > INF_NEAR ? inflate_stats().far_matches : inflate_stats().near_matches)++); INF_STAT(inflate_stats().match_bytes += len); INF_STAT(inflate_stats().dist_hist[32 - __builtin_clz(dist | 1u) > 15 ? 15 : 32 - __builtin_clz(dist | 1u)]++);
+    INF_STAT(inflate_stats().match_bytes += len); INF_STAT(inflate_stats().dist_hist[32 - __builtin_clz(dist | 1u) > 15 ? 15 : 32 - __builtin_clz(dist | 1u)]++);
     INF_STAT(dist > INF_NEAR ? inflate_stats().far_len_hist[len < 4 ? 0 : len <= 8 ? 1 : len <= 16 ? 2 : len <= 32 ? 3 : len <= 64 ? 4 : 5]++ : 0);
+    INF_STAT(dist > INF_NEAR && (unsigned long long)o.flushed - (pos - dist + len) < inflate_stats().far_min_slack ? inflate_stats().far_min_slack = (unsigned long long)o.flushed - (pos - dist + len) : 0);
+    INF_STAT(dist < len ? (dist < 64u ? inflate_stats().overlap_recip : inflate_stats().overlap_sub)++ : 0); INF_STAT(inflate_stats().near_matches += dist < len ? 1 : 0);
     // (the loops count wave-uniform passes of one byte per lane and predicate the lanes inside: a loop whose trip count differs per lane
     //  makes the compiler wrap the whole function in exec-mask bookkeeping, and this code is bound by the scalar unit)
     // len >= 3 (RFC 1951), so every loop runs at least once: do-while saves the entry test
     if (dist >= len) {                                                 // no overlap
         if (dist <= INF_NEAR) {                                        // the common case: ring to ring
+            INF_STAT(inflate_stats().near_matches++);                      // (counted in the branch that is taken: the tests pin the border)
             if (INF_LANE < len) S.ring[(pos + INF_LANE) & INF_RMASK] = S.ring[(pos + INF_LANE - dist) & INF_RMASK];      // (most matches fit one pass)
             for (uint32_t b = INF_W; b < len; b += INF_W) {
                 const uint32_t j = b + INF_LANE;
                 if (j < len) S.ring[(pos + j) & INF_RMASK] = S.ring[(pos + j - dist) & INF_RMASK];
             }
         } else {
+            INF_STAT(inflate_stats().far_matches++);
 #if defined(__HIP_DEVICE_COMPILE__)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -497,6 +521,7 @@ RSQC_INF_FN bool inflate_one_symbol(InflateScratch &S, InflateIn &bi, InflateOut
         uint32_t len;
         const uint32_t s = inflate_symbol_slow(bi.head32(), S.lcount, S.lfirst, S.lidx, S.lsym, len);
         if (s == 0xFFFFu) { status = INF_ERR_SYMBOL; return false; }
+        INF_STAT(inflate_stats().long_ll[len]++);
         e = inflate_entry(INF_T_LITLEN, s, len);
     }
     bi.drop(e & 15u);
@@ -517,6 +542,7 @@ RSQC_INF_FN bool inflate_one_symbol(InflateScratch &S, InflateIn &bi, InflateOut
         uint32_t dl;
         const uint32_t ds = inflate_symbol_slow(bi.head32(), S.dcount, S.dfirst, S.didx, S.dsym, dl);
         if (ds == 0xFFFFu) { status = INF_ERR_SYMBOL; return false; }
+        INF_STAT(inflate_stats().long_d[dl]++);
         f = inflate_entry(INF_T_DIST, ds, dl);
     }
     if (f & INF_E_INVALID) { status = INF_ERR_SYMBOL; return false; }
@@ -534,10 +560,12 @@ RSQC_INF_FN bool inflate_one_symbol(InflateScratch &S, InflateIn &bi, InflateOut
 // inflate_round stands on it).  false: not such a symbol -- the buffered bits end inside it, nobody owns the code
 RSQC_INF_FN bool inflate_long_code_here(InflateScratch &S, InflateIn &bi, uint32_t off, uint32_t avail, uint32_t &kind, uint32_t &adv, uint32_t &ol, uint32_t &val) {
     const uint64_t w = bi.bits_at(off);
+    INF_STAT(inflate_stats().long_here_lanes |= INF_UNI(S.lfast[(uint32_t)w & ((1u << INF_LBITS) - 1u)]) ? 0ull : 1ull << off);
     if (INF_UNI(S.lfast[(uint32_t)w & ((1u << INF_LBITS) - 1u)])) return false;   // (not a long code: the symbol runs past the buffered bits, or is undefined)
     uint32_t len;
     const uint32_t sy = inflate_symbol_slow((uint32_t)w, S.lcount, S.lfirst, S.lidx, S.lsym, len);
     if (sy == 0xFFFFu) return false;
+    INF_STAT(inflate_stats().long_ll[len]++);
     const uint32_t e = inflate_entry(INF_T_LITLEN, sy, len);
     ol = 0; val = 0;
     if (e & INF_E_LITERAL) { kind = INF_K_LIT; adv = len; ol = 1; val = (e >> 8) & 0xFFu; }
@@ -553,6 +581,7 @@ RSQC_INF_FN bool inflate_long_code_here(InflateScratch &S, InflateIn &bi, uint32
             uint32_t dl;
             const uint32_t ds = inflate_symbol_slow((uint32_t)w2, S.dcount, S.dfirst, S.didx, S.dsym, dl);
             if (ds == 0xFFFFu) return false;
+            INF_STAT(inflate_stats().long_d[dl]++);
             f = inflate_entry(INF_T_DIST, ds, dl);
         }
         if (f & INF_E_INVALID) return false;
@@ -666,6 +695,17 @@ RSQC_INF_FN bool inflate_round(InflateScratch &S, InflateIn &bi, InflateOut &o, 
     bool stopped = off < 64u;                                               // the walk met a symbol it cannot take, at bit offset off
     const uint32_t stopped_at = a;
     INF_STAT(inflate_stats().rounds++); INF_STAT(inflate_stats().round_symbols += (unsigned)__builtin_popcountll(starts)); INF_STAT(inflate_stats().slow_symbols += stopped ? 1 : 0);
+#if defined(INF_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+    {
+        InflateStats &st = inflate_stats();
+        if ((unsigned long long)__builtin_popcountll(starts) > st.max_round_symbols) st.max_round_symbols = (unsigned long long)__builtin_popcountll(starts);
+        for (uint32_t k = 0; k < 64u; ++k) if (((starts >> k) & 1ull) && (INF_AT(PK, k) & 0xFFu) > st.max_symbol_bits) st.max_symbol_bits = INF_AT(PK, k) & 0xFFu;
+        if (stopped && (stopped_at >> 8) == (uint32_t)INF_K_OTHER) {
+            st.stops_other++; st.stop_lanes |= 1ull << off;
+            if (INF_UNI(S.lfast[(uint32_t)bi.bits_at(off) & ((1u << INF_LBITS) - 1u)]) && (stopped_at & 0xFFu) && off + (stopped_at & 0xFFu) > avail) st.past_avail++;
+        }
+    }
+#endif
     if (starts) {
         // every symbol's place in the output
         InfVec X, INC;
@@ -679,6 +719,7 @@ RSQC_INF_FN bool inflate_round(InflateScratch &S, InflateIn &bi, InflateOut &o, 
             starts &= (1ull << c) - 1ull;
             total = INF_GET(INC, c) - INF_GET(X, c);
             off = c; stopped = false;                                       // (the lane index IS the bit offset: the next round starts at that symbol)
+            INF_STAT(inflate_stats().cuts++); INF_STAT(inflate_stats().cut_lanes |= 1ull << c);
         }
         if (o.pos + total > o.out_len) { status = INF_ERR_OUTPUT; return false; }
         InfVec ISLIT, ISMATCH;
@@ -703,11 +744,16 @@ RSQC_INF_FN bool inflate_round(InflateScratch &S, InflateIn &bi, InflateOut &o, 
             InfVec DEP;
             INF_FOREACH(k) { (void)k; INF_AT(DEP, k) = (INF_AT(ISMATCH, k) && INF_AT(VAL, k) < INF_AT(INC, k)) ? 1u : 0u; }
             one_pass = !inf_ballot(DEP);
+            INF_STAT(inflate_stats().one_pass_dep += one_pass ? 0 : 1);
         }
+        INF_STAT(inflate_stats().one_pass += one_pass ? 1 : 0);
+        INF_STAT((unsigned long long)__builtin_popcountll(match) > inflate_stats().max_round_matches ? inflate_stats().max_round_matches = (unsigned long long)__builtin_popcountll(match) : 0);
         if (one_pass) {
             InfVec FAR_;
             INF_FOREACH(k) { (void)k; INF_AT(FAR_, k) = (INF_AT(ISMATCH, k) && INF_AT(VAL, k) > INF_NEAR) ? 1u : 0u; }
+            INF_STAT(inflate_stats().one_pass_matches += (unsigned)__builtin_popcountll(match)); INF_STAT(inflate_stats().one_pass_far_matches += (unsigned)__builtin_popcountll(inf_ballot(FAR_)));
             if (inf_ballot(FAR_)) {                                         // sources that left the ring are read from the stream (see inflate_copy)
+                INF_STAT(inflate_stats().one_pass_far++);
 #if defined(__HIP_DEVICE_COMPILE__)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -785,6 +831,7 @@ RSQC_INF_FN int inflate_block(InflateScratch &S, const uint8_t *in, uint32_t in_
     for (;;) {
         bi.refill();
         const uint32_t bfinal = bi.take(1), btype = bi.take(2);
+        INF_STAT(btype < 3u ? inflate_stats().blocks[btype]++ : 0);
         if (btype == 0u) {                                          // stored: LEN, ~LEN on a byte boundary, then the bytes
             bi.drop(bi.avail() & 7u);
             bi.refill();
@@ -835,6 +882,15 @@ RSQC_INF_FN int inflate_block(InflateScratch &S, const uint8_t *in, uint32_t in_
                 }
                 if (INF_UNI(S.lens[256]) == 0u) return INF_ERR_TABLE;                // no end-of-block code
             }
+#if defined(INF_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+            {                                                       // Kraft sum of this block's distance lengths against the block before it
+                static bool prev_full = false;
+                uint32_t kraft = 0;
+                for (uint32_t s = 0; s < ndist; ++s) if (S.lens[nlit + s]) kraft += 1u << (15u - S.lens[nlit + s]);
+                if (!kraft && prev_full) inflate_stats().empty_dist_after_full++;
+                prev_full = kraft == (1u << 15);
+            }
+#endif
             if (!INF_BUILD(S.lens, nlit, S.lcount, S.lsym, S.lfirst, S.lidx, S.lfast, INF_LBITS, S.offs, INF_T_LITLEN)) return INF_ERR_TABLE;
             if (!INF_BUILD(S.lens + nlit, ndist, S.dcount, S.dsym, S.dfirst, S.didx, S.dfast, INF_DBITS, S.offs, INF_T_DIST)) return INF_ERR_TABLE;
             // ---- the symbols, in rounds (inflate_round)

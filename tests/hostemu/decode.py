@@ -19,7 +19,8 @@ _ROOT = os.path.dirname(os.path.dirname(_HERE))
 VARIANTS = {"": (), "no_par_commit": ("-DINF_PAR_COMMIT_CFG=0",), "no_inwalk": ("-DINF_INWALK_CFG=0",),
             "all": ("-DINF_PAR_COMMIT_CFG=0", "-DINF_INWALK_CFG=0"),
             "vwalk1": ("-DINF_VWALK_CFG=1",), "vwalk2": ("-DINF_VWALK_CFG=2",), "vwalk3": ("-DINF_VWALK_CFG=3",),
-            "vwalk3_no_inwalk": ("-DINF_VWALK_CFG=3", "-DINF_INWALK_CFG=0")}
+            "vwalk3_no_inwalk": ("-DINF_VWALK_CFG=3", "-DINF_INWALK_CFG=0"),
+            "stats": ("-DINF_STATS",)}                     # the product's configuration with the counters of rsqc_inflate.h (inflate_stats)
 
 
 def build(variant=""):
@@ -47,6 +48,31 @@ def inflate(comp, n, crc, variant=""):
     out = C.create_string_buffer(n + 64)
     rc = lib(variant).emu_inflate(comp, len(comp), out, n, crc & 0xFFFFFFFF)
     return rc, out.raw[:n]
+
+
+# InflateStats of rsqc_inflate.h, in declaration order: (name, words)
+STAT_FIELDS = (("near_matches", 1), ("far_matches", 1), ("match_bytes", 1), ("rounds", 1), ("round_symbols", 1), ("slow_symbols", 1), ("dist_hist", 16),
+               ("far_len_hist", 10), ("long_ll", 16), ("long_d", 16), ("cuts", 1), ("cut_lanes", 1), ("stops_other", 1), ("stop_lanes", 1), ("past_avail", 1),
+               ("max_symbol_bits", 1), ("one_pass", 1), ("one_pass_dep", 1), ("one_pass_far", 1), ("overlap_recip", 1), ("overlap_sub", 1), ("blocks", 3),
+               ("empty_dist_after_full", 1), ("full_flushes", 1), ("last_flush", 1), ("far_min_slack", 1), ("max_round_symbols", 1), ("max_round_matches", 1),
+               ("one_pass_matches", 1), ("one_pass_far_matches", 1), ("long_here_lanes", 1))
+
+
+def inflate_with_stats(comp, n, crc):
+    """(status, bytes, stats) of one stream through the "stats" variant: stats maps the counters of InflateStats to ints (lists for
+    the arrays), counted over this stream alone."""
+    l = lib("stats")
+    words = sum(w for _f, w in STAT_FIELDS)
+    assert l.emu_inflate_stats(None, 0, 1) == words, "STAT_FIELDS does not match InflateStats"
+    out = C.create_string_buffer(n + 64)
+    rc = l.emu_inflate(comp, len(comp), out, n, crc & 0xFFFFFFFF)
+    buf = (C.c_ulonglong * words)()
+    l.emu_inflate_stats(buf, words, 1)
+    st, at = {}, 0
+    for f, w in STAT_FIELDS:
+        st[f] = int(buf[at]) if w == 1 else [int(x) for x in buf[at:at + w]]
+        at += w
+    return rc, out.raw[:n], st
 
 
 class TagSpec(C.Structure):

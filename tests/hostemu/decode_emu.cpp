@@ -24,6 +24,22 @@ int emu_inflate(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_l
     return inflate_block(S, padded.data() + 3, in_len, out, out_len, crc32);
 }
 
+// the counters of the -DINF_STATS build (rsqc_inflate.h: InflateStats, as unsigned long long words in declaration order): copies up
+// to `cap` words into `out`, returns how many there are; reset != 0 clears them afterwards.  -1: not a stats build.
+extern "C" __attribute__((visibility("default")))
+int emu_inflate_stats(unsigned long long *out, int cap, int reset) {
+#if defined(INF_STATS)
+    InflateStats &st = inflate_stats();
+    const int n = (int)(sizeof(InflateStats) / sizeof(unsigned long long));
+    if (out) memcpy(out, &st, sizeof(unsigned long long) * (size_t)std::min(n, cap));
+    if (reset) { st = InflateStats{}; st.far_min_slack = ~0ull; }
+    return n;
+#else
+    (void)out; (void)cap; (void)reset;
+    return -1;
+#endif
+}
+
 // the 64-lane form of inflate_flush's CRC step (pieces, right alignment, six-level tree), with the lanes as an array:
 // checks the arithmetic the device build uses where the one-lane host build takes a shortcut
 extern "C" __attribute__((visibility("default")))

@@ -10,6 +10,10 @@
 // has no GPU: the host build is where that can be looked for.
 //
 //   inflate_fuzz <cases> <seed>      exit 0 = every case agreed; the sanitizers abort the process on a finding
+//   inflate_fuzz --corpus FILE [mutations per stream] [seed]
+//       the streams of a file written by tests/test_inflate_crafted.py (hand-built DEFLATE streams aimed at the decoder's limits,
+//       tests/hostemu/inflate_cases.py) -- records of u32 payload bytes, u32 ISIZE, u32 CRC-32, payload: each one clean, which must
+//       inflate like zlib, then under the mutations above, with the same verdicts
 #include <signal.h>
 #include <unistd.h>
 #include <zlib.h>
@@ -81,26 +85,12 @@ static void on_alarm(int) {
     _exit(3);
 }
 
-int main(int argc, char **argv) {
-    const long cases = argc > 1 ? atol(argv[1]) : 2000;
-    g_state = argc > 2 ? strtoull(argv[2], nullptr, 10) * 2 + 1 : 1;
-    signal(SIGALRM, on_alarm);
-    InflateScratch *S = new InflateScratch;                                            // (heap: the sanitizer sees its end)
-    inflate_crc_init(*S);
-    long agreed_ok = 0, agreed_err = 0, lenient = 0;
-    std::vector<uint8_t> base, comp;
-    for (long c = 0; c < cases; ++c) {
-        g_case = c;
-        if (c % 8 == 0) {                                                              // a new clean stream every few cases
-            static const int strat[4] = {Z_DEFAULT_STRATEGY, Z_FIXED, Z_HUFFMAN_ONLY, Z_RLE};
-            static const int lvl[4] = {1, 6, 9, 0};
-            base = payload(rnd(5), 1 + rnd(rnd(4) ? 6000 : 65536));
-            comp = deflate_raw(base, lvl[rnd(4)], strat[rnd(4)], rnd(3) == 0);
-        }
-        std::vector<uint8_t> in = comp;
-        uint32_t isize = (uint32_t)base.size();
-        uint32_t crc = (uint32_t)crc32(0, base.data(), (uInt)base.size());
-        switch (rnd(10)) {
+static long g_agreed_ok = 0, g_agreed_err = 0, g_lenient = 0;
+
+// damages the stream (kind 0 leaves it as it is); sets g_what
+static void mutate(std::vector<uint8_t> &in, uint32_t &isize, uint32_t kind) {
+    if (in.empty()) { g_what = "clean"; return; }
+    switch (kind) {
         case 0: g_what = "clean"; break;
         case 1: g_what = "bit flip"; in[rnd((uint32_t)in.size())] ^= (uint8_t)(1u << rnd(8)); break;
         case 2: g_what = "bit flips"; for (uint32_t k = 0, n = 2 + rnd(8); k < n; ++k) in[rnd((uint32_t)in.size())] ^= (uint8_t)(1u << rnd(8)); break;
@@ -111,8 +101,13 @@ int main(int argc, char **argv) {
         case 7: g_what = "garbage behind a dynamic header"; for (auto &b : in) b = (uint8_t)rnd(256); if (!in.empty()) in[0] = (uint8_t)((in[0] & ~7u) | 5u); break;
         case 8: g_what = "wrong ISIZE"; isize = rnd(4) ? isize + 1 + rnd(300) : (isize > 1 ? rnd(isize) : 0); break;
         default: g_what = "zero bytes"; for (uint32_t k = 0, at = rnd((uint32_t)in.size()), n = 1 + rnd(64); k < n && at + k < in.size(); ++k) in[at + k] = 0; break;
-        }
-        if (isize > 65536u) isize = 65536u;
+    }
+    if (isize > 65536u) isize = 65536u;
+}
+
+// the decoder against zlib on one (possibly damaged) stream; false = they disagree (reported)
+static bool judge(InflateScratch *S, long c, const std::vector<uint8_t> &in, uint32_t isize, uint32_t crc) {
+    {
         std::vector<uint8_t> want;
         const bool z_ok = zlib_inflates(in, isize, want) && (uint32_t)crc32(0, want.data(), (uInt)want.size()) == crc;
         // exact-size heap copies: the payload with the 16 bytes the decoder may look ahead, ISIZE bytes of output
@@ -124,16 +119,73 @@ int main(int argc, char **argv) {
         const int rc = inflate_block(*S, pin + 3, (uint32_t)in.size(), pout, isize, crc);
         alarm(0);
         bool good;
-        if (z_ok) { good = rc == 0 && (isize == 0 || memcmp(pout, want.data(), isize) == 0); agreed_ok += good; }
-        else if (rc != 0) { good = true; ++agreed_err; }
-        else { good = (uint32_t)crc32(0, pout, isize) == crc; lenient += good; }
+        if (z_ok) { good = rc == 0 && (isize == 0 || memcmp(pout, want.data(), isize) == 0); g_agreed_ok += good; }
+        else if (rc != 0) { good = true; ++g_agreed_err; }
+        else { good = (uint32_t)crc32(0, pout, isize) == crc; g_lenient += good; }
         if (!good) {
             fprintf(stderr, "inflate_fuzz: case %ld (%s): zlib %s, decoder status %d (payload %zu bytes, ISIZE %u)\n", c, g_what, z_ok ? "inflates it" : "rejects it", rc, in.size(), isize);
-            return 1;
+            return false;
         }
         free(pin); free(pout);
     }
-    printf("inflate_fuzz: %ld cases: %ld inflated like zlib, %ld rejected like zlib, %ld that only zlib rejects (right bytes by the CRC)\n", cases, agreed_ok, agreed_err, lenient);
+    return true;
+}
+
+static int run_corpus(InflateScratch *S, const char *path, long per_stream) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "inflate_fuzz: cannot open %s\n", path); return 2; }
+    long streams = 0, c = 0;
+    for (;;) {
+        uint32_t head[3];
+        const size_t got = fread(head, 4, 3, f);
+        if (got == 0) break;
+        std::vector<uint8_t> comp(head[0]);
+        if (got != 3 || head[1] > 65536u || (head[0] && fread(comp.data(), 1, head[0], f) != head[0])) { fprintf(stderr, "inflate_fuzz: %s: bad record %ld\n", path, streams); fclose(f); return 2; }
+        for (long m = 0; m <= per_stream; ++m, ++c) {
+            g_case = c;
+            std::vector<uint8_t> in = comp;
+            uint32_t isize = head[1];
+            g_what = "clean";
+            if (m) mutate(in, isize, 1 + rnd(9));
+            const long ok_before = g_agreed_ok;
+            if (!judge(S, c, in, isize, head[2])) { fprintf(stderr, "inflate_fuzz: ... stream %ld of the corpus\n", streams); fclose(f); return 1; }
+            if (!m && g_agreed_ok == ok_before) { fprintf(stderr, "inflate_fuzz: stream %ld of the corpus: zlib does not inflate the clean stream\n", streams); fclose(f); return 1; }
+        }
+        ++streams;
+    }
+    fclose(f);
+    printf("inflate_fuzz: corpus of %ld streams, %ld cases: %ld inflated like zlib, %ld rejected like zlib, %ld that only zlib rejects (right bytes by the CRC)\n", streams, c, g_agreed_ok, g_agreed_err, g_lenient);
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    signal(SIGALRM, on_alarm);
+    InflateScratch *S = new InflateScratch;                                            // (heap: the sanitizer sees its end)
+    inflate_crc_init(*S);
+    if (argc > 2 && !strcmp(argv[1], "--corpus")) {
+        g_state = argc > 4 ? strtoull(argv[4], nullptr, 10) * 2 + 1 : 1;
+        const int rc = run_corpus(S, argv[2], argc > 3 ? atol(argv[3]) : 20);
+        delete S;
+        return rc;
+    }
+    const long cases = argc > 1 ? atol(argv[1]) : 2000;
+    g_state = argc > 2 ? strtoull(argv[2], nullptr, 10) * 2 + 1 : 1;
+    std::vector<uint8_t> base, comp;
+    for (long c = 0; c < cases; ++c) {
+        g_case = c;
+        if (c % 8 == 0) {                                                              // a new clean stream every few cases
+            static const int strat[4] = {Z_DEFAULT_STRATEGY, Z_FIXED, Z_HUFFMAN_ONLY, Z_RLE};
+            static const int lvl[4] = {1, 6, 9, 0};
+            base = payload(rnd(5), 1 + rnd(rnd(4) ? 6000 : 65536));
+            comp = deflate_raw(base, lvl[rnd(4)], strat[rnd(4)], rnd(3) == 0);
+        }
+        std::vector<uint8_t> in = comp;
+        uint32_t isize = (uint32_t)base.size();
+        const uint32_t crc = (uint32_t)crc32(0, base.data(), (uInt)base.size());
+        mutate(in, isize, rnd(10));
+        if (!judge(S, c, in, isize, crc)) return 1;
+    }
+    printf("inflate_fuzz: %ld cases: %ld inflated like zlib, %ld rejected like zlib, %ld that only zlib rejects (right bytes by the CRC)\n", cases, g_agreed_ok, g_agreed_err, g_lenient);
     delete S;
     return 0;
 }
