@@ -631,6 +631,39 @@ typedef struct rsqc_sort_info {
 RSQC_API int rsqc_sort_begin(rsqc_ctx *ctx);
 RSQC_API int rsqc_sort_end(rsqc_ctx *ctx, rsqc_sort_info *out);
 
+/* ---- reads per splice junction (additive to ABI 6) ---------------------------------------------------------------------
+ * Between rsqc_junctions_begin and the end of the pass every batch that the per-read kernels run also leaves its splice-junction
+ * INSTANCES on the device (one extra kernel per batch; no other kernel, output or launch changes), and rsqc_junctions_end orders
+ * and reduces them to one row per junction.  The contract, in integers:
+ *   population   a record contributes iff (flag & (0x4 | 0x100 | 0x200 | 0x800)) == 0 and its segment's tid is in [0, n_contigs).
+ *                Nothing else gates it: not -q, the tag filters, --exclude-chimeric, --legacy, --unpaired, --stranded, nor the
+ *                duplicate flag.
+ *   walk         p = pos (64 bits); the operations in order (a wide record: its true count): an N of length L >= 1 is one instance
+ *                (tid, start = p + 1, end = p + L) -- 1-based closed, the intron's first and last base, STAR's SJ.out.tab
+ *                convention; M D N = X advance p.  An N of length 0 yields nothing; an instance whose end exceeds 2^31 - 1 is dropped;
+ *                an N without an aligned block on one side still counts.
+ *   overhang     of an instance: min(left, right), the sums of the M = X lengths between the previous N (of any length; or the
+ *                record's start) and this N, and from this N to the next N (or the record's end).  D I S H P add nothing.
+ *   table        one row per distinct (tid, start, end), ascending in that order: reads = instances, hq_reads = instances of records
+ *                with mapq >= params.mapq_threshold (the complement of the "Low Mapping Quality" test), max_overhang = the largest
+ *                overhang among them.  It does not depend on the order of the records or on how they are cut into batches.
+ * rsqc_junctions_begin: after rsqc_set_annotation and before the pass's first submit (RSQC_ERR_ARG otherwise); with rsqc_sort_begin in
+ * either order -- the instances are then taken from the sorted output batches.  rsqc_junctions_end: behind rsqc_finalize or
+ * rsqc_finalize_device of that pass (RSQC_ERR_ARG otherwise); a second call returns the same table without new device work.  The
+ * arrays are owned by the context and stay valid until its next rsqc_reset, rsqc_clear_inputs or rsqc_destroy, which also end the
+ * mode and forget the instances.  The collection (16 bytes per instance) grows by doubling from 65 536 instances (environment:
+ * RSQC_JUNCTION_CAP0) to a bound the host computes without the device -- half the CIGAR operations submitted so far; an instance
+ * beyond it, or 2^32 - 16 instances and more, is RSQC_ERR_CAPACITY, never a partial table.  Not exchanged by rsqc_reduce_* /
+ * rsqc_group_*: a sharded run keeps one table per context.                                                                        */
+typedef struct rsqc_junction_table {
+    uint64_t n, instances, population; /* rows; instances; contributing records                                       */
+    const int32_t *tid, *start, *end;  /* [n] contig id, first and last base of the intron (1-based closed)           */
+    const uint32_t *reads, *hq_reads, *max_overhang;   /* [n]                                                         */
+    double extract_ms, sort_ms, reduce_ms;   /* the per-batch kernels (HIP events); the two sort stages; heads, scan and rows (host clocks) */
+} rsqc_junction_table;
+RSQC_API int rsqc_junctions_begin(rsqc_ctx *ctx);
+RSQC_API int rsqc_junctions_end(rsqc_ctx *ctx, rsqc_junction_table *out);
+
 RSQC_API const char *rsqc_strerror(int code);
 RSQC_API const char *rsqc_last_error(rsqc_ctx *ctx);
 RSQC_API const char *rsqc_counter_name(int counter);   /* the reference's Metrics key  */

@@ -190,6 +190,12 @@ class SortInfo(C.Structure):
                 ("key_ms", C.c_double), ("sort_ms", C.c_double), ("gather_ms", C.c_double), ("was_sorted", C.c_int32)]
 
 
+class JunctionTable(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("instances", C.c_uint64), ("population", C.c_uint64),
+                ("tid", _P), ("start", _P), ("end", _P), ("reads", _P), ("hq_reads", _P), ("max_overhang", _P),
+                ("extract_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double)]
+
+
 def ptr(a: np.ndarray | None):
     """numpy array -> void* (None -> NULL).  The caller keeps `a` alive."""
     if a is None:

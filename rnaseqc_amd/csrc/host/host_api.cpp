@@ -74,6 +74,24 @@ HAPI int host_write_reports(void *h, const rsqc_results *r, const char *out_dir,
     return 0;
 }
 
+// --junctions: the `known` rule and the table writer on a GTF and a table given as columns (contigs: the input header's names)
+HAPI int host_write_junctions(const char *gtf, const char *out_path, const char *const *contigs, int n_contigs, uint64_t n, const int32_t *tid, const int32_t *start,
+                              const int32_t *end, const uint32_t *reads, const uint32_t *hq_reads, const uint32_t *max_overhang) {
+    try {
+        Annotation a;
+        a.load_gtf(gtf);
+        std::vector<std::string> c;
+        for (int i = 0; i < n_contigs; ++i) c.emplace_back(contigs[i]);
+        a.flatten(c);
+        JunctionIndex ix;
+        ix.build(a);
+        rsqc_junction_table t{};
+        t.n = n; t.tid = tid; t.start = start; t.end = end; t.reads = reads; t.hq_reads = hq_reads; t.max_overhang = max_overhang;
+        write_junctions(out_path, a, ix, t);
+    } catch (FileError &) { return 10; } catch (GtfError &) { return 11; } catch (...) { return -1; }
+    return 0;
+}
+
 HAPI unsigned host_library_complexity(double dup, double unique, double limit) { return library_complexity(dup, unique, limit); }
 
 struct BamHandle { BamReader reader; HostBatch batch; rsqc_batch view; std::vector<std::string> names; };

@@ -52,6 +52,7 @@ struct Options {
     std::vector<std::string> tags;
     int gpus = 0;                      // --gpus (extension): GPUs to shard the BAM over by contig; 0 = RSQC_GPUS or 1
     std::string bam_list; bool has_bam_list = false;   // --bam-list (extension): a cohort, the positionals are `gtf output`
+    bool junctions = false;            // --junctions (extension): reads per splice junction, <sample>.junctions.tsv (rsqc_junctions_begin / rsqc_junctions_end)
     bool sort = false;                 // --sort (extension): input in any order, put in coordinate order on the GPU (rsqc_sort_begin / rsqc_sort_end)
 };
 
@@ -85,7 +86,8 @@ void usage(std::ostream &o) {
          "      -d[threshold], --detection-threshold=[threshold]  Counts to call a gene detected. Default: 5 reads\n"
          "      --gpus=[N]                        (extension) Shard the BAM by contig over N GPUs of this node; needs [bam].bai. Default: 1\n"
          "      --bam-list=[FILE]                 (extension) A cohort on one GPU: FILE lists one input per line, path[<TAB>sample]; the positionals are [gtf] [output]\n"
-         "      --sort                            (extension) Accept input in any order: the records are put in coordinate order on the GPU before they are counted\n";
+         "      --sort                            (extension) Accept input in any order: the records are put in coordinate order on the GPU before they are counted\n"
+         "      --junctions                       (extension) Count reads per splice junction on the GPU and write [sample].junctions.tsv (one GPU)\n";
 }
 
 long to_long(const std::string &flag, const std::string &v) {
@@ -165,6 +167,7 @@ Options parse(int argc, char **argv) {
         else if (name == "gpus") o.gpus = (int)to_ulong(name, need());
         else if (name == "bam-list") { o.bam_list = need(); o.has_bam_list = true; }
         else if (name == "sort") o.sort = true;
+        else if (name == "junctions") o.junctions = true;
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
         else if (name == "detection-threshold") o.detection = to_ulong(name, need());
         else throw ParseError("Flag could not be matched: " + name);
@@ -500,6 +503,7 @@ struct Session {
     // a cohort: messages carry the sample's name, the reports are written on a thread beside the next sample (one job at most)
     std::string prefix;
     bool async_reports = false;
+    JunctionIndex junction_index;                      // --junctions: the annotation's exon boundaries, built once
     std::future<void> report_job;
     void finish_reports() { if (report_job.valid()) report_job.get(); }
 };
@@ -615,6 +619,16 @@ struct SampleRow { std::string sample, input, format = "not run"; uint64_t recor
 // ---- one sample on one GPU: the input opened and its header read (or taken over from the thread that did), the contig check,
 // the context's inputs (set, kept, or replaced when the header's contigs differ from the sample before), the decode loop,
 // finalize and the reports.  Returns the exit code of a run of this input alone; throws what main() maps to exit codes.
+// the junction table of a sample, copied for the report thread
+struct JunctionCopy {
+    std::vector<int32_t> tid, start, end; std::vector<uint32_t> reads, hq_reads, max_overhang;
+    rsqc_junction_table table{};
+    explicit JunctionCopy(const rsqc_junction_table &t) : tid(t.tid, t.tid + t.n), start(t.start, t.start + t.n), end(t.end, t.end + t.n), reads(t.reads, t.reads + t.n),
+                                                          hq_reads(t.hq_reads, t.hq_reads + t.n), max_overhang(t.max_overhang, t.max_overhang + t.n), table(t) {
+        table.tid = tid.data(); table.start = start.data(); table.end = end.data(); table.reads = reads.data(); table.hq_reads = hq_reads.data(); table.max_overhang = max_overhang.data();
+    }
+};
+
 int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, const std::string &out_dir, SampleRow &row) {
     using std::cerr; using std::cout; using std::endl;
     std::unique_ptr<Input> opened = sample.opened.valid() ? sample.opened.get() : open_input(sample.path, o);
@@ -734,6 +748,8 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     rc = RSQC_OK;
     // --sort: the loops below collect (no per-read kernel runs); rsqc_sort_end orders the records and runs them
     if (o.sort && (rc = rsqc_sort_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    // --junctions: every batch the per-read kernels run leaves its junction instances on the device (under --sort: the sorted batches)
+    if (o.junctions && (rc = rsqc_junctions_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     if (sam_input) {
         // ---- SAM text: the host reads the file (plain) or frames its BGZF blocks, the device does the rest
         rsqc_decode_info di{};
@@ -824,6 +840,8 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     }
     rsqc_results res{};
     if (rc == RSQC_OK) rc = rsqc_finalize(gpu, &res);
+    rsqc_junction_table junctions{};
+    if (o.junctions && rc == RSQC_OK) rc = rsqc_junctions_end(gpu, &junctions);       // (ordered and reduced inside the timed window: the price of the flag)
     S.t_loop1 = Clock::now();
     if (rc == RSQC_ERR_BAD_CIGAR) throw std::invalid_argument("Unrecognized Cigar Op ");
     if (rc == RSQC_ERR_EMPTY_MEDIAN) throw std::range_error("Cannot compute median of an empty list");
@@ -836,6 +854,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (o.verbosity > 1 && sam_input) cout << "(decode: " << (in.fmt == InputFormat::SamBgzf ? "BGZF inflate and SAM text parsing" : "SAM text") << " on the GPU)" << endl;
         else if (o.verbosity > 1 && device_decode) cout << "(decode: BGZF inflate and record parsing on the GPU)" << endl;
         else if (o.verbosity > 1) cout << "(decode threads: " << in.reader->inflate_threads() << " inflate + " << in.reader->parse_threads() << " parse)" << endl;
+        if (o.junctions)
+            cout << "Junctions: population " << junctions.population << ", instances " << junctions.instances << ", rows " << junctions.n << ", extract_ms " << junctions.extract_ms
+                 << ", sort_ms " << junctions.sort_ms << ", reduce_ms " << junctions.reduce_ms << endl;
         cout << "Estimating library complexity..." << endl;
         cout << "Generating report" << endl;
     }
@@ -843,9 +864,12 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     cfg.output_dir = out_dir; cfg.sample_name = sample.name; cfg.sample_given = sample.name_given;
     cfg.use_rpkm = o.rpkm; cfg.write_coverage = o.coverage; cfg.detection_threshold = (unsigned)o.detection;
     cfg.filter_tags = o.tags;
+    const std::string junctions_path = out_dir + "/" + sample.name + ".junctions.tsv";
+    if (o.junctions && !S.junction_index.built) S.junction_index.build(ann);
     if (!S.async_reports) {
         S.t_rep0 = Clock::now();
         write_reports(cfg, ann, res, visit);
+        if (o.junctions) write_junctions(junctions_path, ann, S.junction_index, junctions);
         S.t_rep1 = Clock::now();
         return 0;
     }
@@ -854,9 +878,11 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     S.finish_reports();
     timer.armed = false;
     std::shared_ptr<ResultsCopy> copy(new ResultsCopy(res));
+    std::shared_ptr<JunctionCopy> jcopy(o.junctions ? new JunctionCopy(junctions) : nullptr);      // (the context's arrays end with its next reset)
+    const JunctionIndex *jindex = &S.junction_index;
     const std::string prefix = S.prefix;
-    S.report_job = std::async(std::launch::async, [cfg, &ann, copy, visit, &row, t_open, prefix] {
-        try { write_reports(cfg, ann, copy->res, visit); }
+    S.report_job = std::async(std::launch::async, [cfg, &ann, copy, jcopy, jindex, junctions_path, visit, &row, t_open, prefix] {
+        try { write_reports(cfg, ann, copy->res, visit); if (jcopy) write_junctions(junctions_path, ann, *jindex, jcopy->table); }
         catch (...) { row.exit_code = explain_exception(prefix); }
         row.seconds = seconds_between(t_open, Clock::now());
     });
@@ -1139,6 +1165,12 @@ int main(int argc, char **argv) {
             bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
             if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
             if (many_gpus) throw ValidationError("--sort runs on one GPU (--gpus, RSQC_GPUS and RSQC_GPU_LIST shard a coordinate-sorted, indexed BAM)");
+        }
+        if (o.junctions) {
+            // one table per context: the per-contig tables of shards would only need concatenating, but that path is not built
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--junctions runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
         }
         // a cohort: the list is read and checked before anything else is touched
         std::vector<Sample> samples;

@@ -385,4 +385,38 @@ void write_reports(const ReportConfig &cfg, Annotation &ann, const rsqc_results 
     crew.wait();
 }
 
+void JunctionIndex::build(const Annotation &ann) {
+    ends.clear(); starts.clear();
+    for (const auto &r : ann.rows) {
+        if (r.is_gene || r.excluded || r.chrom < 0) continue;
+        if ((size_t)r.chrom >= ends.size()) { ends.resize((size_t)r.chrom + 1); starts.resize((size_t)r.chrom + 1); }
+        ends[(size_t)r.chrom][r.end].push_back(r.gene_key);
+        starts[(size_t)r.chrom][r.start].push_back(r.gene_key);
+    }
+    built = true;
+}
+
+bool JunctionIndex::known(int chrom, long long start, long long end) const {
+    if (chrom < 0 || (size_t)chrom >= ends.size()) return false;
+    const auto e = ends[(size_t)chrom].find(start - 1);
+    if (e == ends[(size_t)chrom].end()) return false;
+    const auto s = starts[(size_t)chrom].find(end + 1);
+    if (s == starts[(size_t)chrom].end()) return false;
+    for (uint32_t g : e->second) if (std::find(s->second.begin(), s->second.end(), g) != s->second.end()) return true;
+    return false;
+}
+
+void write_junctions(const std::string &path, const Annotation &ann, const JunctionIndex &index, const rsqc_junction_table &t) {
+    std::ofstream f(path);
+    f << "contig\tstart\tend\treads\thq_reads\tmax_overhang\tknown" << NL;
+    for (uint64_t k = 0; k < t.n; ++k) {
+        const int32_t tid = t.tid[k];
+        const bool in_range = tid >= 0 && (size_t)tid < ann.contig_names.size();
+        const int chrom = in_range && (size_t)tid < ann.chrom_of_contig.size() ? ann.chrom_of_contig[(size_t)tid] : -1;
+        if (in_range) f << ann.contig_names[(size_t)tid]; else f << tid;
+        f << '\t' << t.start[k] << '\t' << t.end[k] << '\t' << t.reads[k] << '\t' << t.hq_reads[k] << '\t' << t.max_overhang[k] << '\t'
+          << (index.known(chrom, t.start[k], t.end[k]) ? 1 : 0) << NL;
+    }
+}
+
 }  // namespace rsqc_host

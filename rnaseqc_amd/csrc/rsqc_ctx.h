@@ -136,6 +136,18 @@ struct SortState {
     std::vector<uint64_t> batch_rec0, batch_pool0;   // first record / first operation of every collected batch
 };
 
+// --junctions (rsqc_junctions_begin / rsqc_junctions_end, rsqc_junction_api.cpp): the instances of the pass, three columns that grow by
+// doubling to the host's bound; the finished table on the host
+struct JunctionState {
+    bool active = false, done = false;
+    uint64_t cap = 0, cap0 = 0, bound = 0;             // instances the columns hold; the first size; half the operations submitted so far
+    DevBuf key_hi, end, info, cursor;                  // cursor: u64 instances, u64 contributing records
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;   // around every batch's extraction
+    std::vector<int32_t> tid, start, end_h;
+    std::vector<uint32_t> reads, hq_reads, max_overhang;
+    rsqc_junction_table table{};
+};
+
 }  // namespace rsqc
 using namespace rsqc;            // (every unit that sees this header is host code of the library)
 
@@ -228,6 +240,7 @@ struct rsqc_ctx {
 
     DecodeState dec;
     SortState sort;
+    JunctionState junc;
 
     // host results
     std::vector<uint64_t> h_fcount;
@@ -262,6 +275,9 @@ const char *device_error_text(int err);
 // collecting mode: the batch's records are appended to the collection instead of being run (rsqc_sort_api.cpp)
 int sort_append(rsqc_ctx *c, UploadedBatch *u);
 void sort_drop(rsqc_ctx *c);                   // leaves the collecting mode and frees the collection (hipFree waits for the device)
+// --junctions: the batch's instances appended to the collection, on the main stream (rsqc_junction_api.cpp)
+int junction_extract(rsqc_ctx *c, const UploadedBatch *u, const DevBatch &d);
+void junction_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the instances
 
 template <class T>
 int upload(rsqc_ctx *c, std::vector<DevBuf> &owner, const T *host, size_t n, const T **out, bool from_pool = false) {

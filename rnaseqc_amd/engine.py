@@ -73,6 +73,8 @@ def load_library():
         lib.rsqc_decode_submit_text.argtypes = [vp, vp, C.c_uint64, C.POINTER(abi.DecodeWindow)]
         lib.rsqc_sort_begin.argtypes = [vp]
         lib.rsqc_sort_end.argtypes = [vp, C.POINTER(abi.SortInfo)]
+        lib.rsqc_junctions_begin.argtypes = [vp]
+        lib.rsqc_junctions_end.argtypes = [vp, C.POINTER(abi.JunctionTable)]
         _lib = lib
     return _lib
 
@@ -84,7 +86,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_group_create", "rsqc_group_reduce", "rsqc_group_info", "rsqc_group_destroy", "rsqc_refresh_results", "rsqc_finalize_device", "rsqc_host_alloc", "rsqc_host_free", "rsqc_strerror",
     "rsqc_last_error", "rsqc_counter_name", "rsqc_version", "rsqc_qname_hash", "rsqc_qname_hash2",
     "rsqc_decode_begin", "rsqc_decode_submit", "rsqc_decode_end", "rsqc_decode_begin_sam", "rsqc_decode_submit_text",
-    "rsqc_sort_begin", "rsqc_sort_end",
+    "rsqc_sort_begin", "rsqc_sort_end", "rsqc_junctions_begin", "rsqc_junctions_end",
 ]
 
 
@@ -239,6 +241,22 @@ class Engine:
         info = abi.SortInfo()
         self._check(self._l.rsqc_sort_end(self._h, C.byref(info)))
         return {f: getattr(info, f) for f, _ in abi.SortInfo._fields_}
+
+    # ---- reads per splice junction (rsqc_junctions_*) -------------------------------------------------------------
+    def junctions_begin(self):
+        """From here to the end of the pass every batch that is run also leaves its splice-junction instances on the device."""
+        self._check(self._l.rsqc_junctions_begin(self._h))
+
+    def junctions_end(self) -> dict:
+        """After finalize() / finalize_device(): the junction table as numpy arrays (copies) -- tid, start, end (int32), reads,
+        hq_reads, max_overhang (uint32), one entry per row in (tid, start, end) order -- and the scalars of rsqc_junction_table."""
+        t = abi.JunctionTable()
+        self._check(self._l.rsqc_junctions_end(self._h, C.byref(t)))
+        n = int(t.n)
+        out = {f: abi._view(getattr(t, f), n, np.int32) for f in ("tid", "start", "end")}
+        out.update({f: abi._view(getattr(t, f), n, np.uint32) for f in ("reads", "hq_reads", "max_overhang")})
+        out.update(n=n, instances=int(t.instances), population=int(t.population), extract_ms=t.extract_ms, sort_ms=t.sort_ms, reduce_ms=t.reduce_ms)
+        return out
 
     def read_device(self, ptr, count, dtype):
         """count items of dtype from a device pointer of this context (tests): hipMemcpy of the HIP runtime the library itself is
