@@ -78,7 +78,8 @@ struct GcCandidates {
     uint32_t *count; uint32_t cap;
     uint32_t *h2;                // second name hash of the record (rsqc_batch.qhash2; zeros for a batch without)
 };
-#if defined(__HIPCC__)
+// (no device-only guard: the two helpers are plain integer and double code, and the host SIMT emulation of the tests runs them as they are --
+//  tests/hostemu/gc_emu.cpp; this header is only ever compiled by hipcc or on top of tests/hostemu/wavemu.h, which supply __device__)
 // bases of [s, e) (0-based, inside the contig) that are G/C
 __device__ __forceinline__ uint32_t gc_count(const DevReference &R, int contig, int64_t s, int64_t e) {
     if (e <= s) return 0u;
@@ -100,7 +101,6 @@ __device__ __forceinline__ double gc_value(uint32_t k, uint64_t size) {
     for (uint32_t i = 0; i < k; ++i) c += inc;
     return c;
 }
-#endif
 
 // one (gene, read name) pair as the per-record kernels emit it.  Round 6: an array of these 16-byte structures -- ONE
 // global_store_dwordx4 per pair in the per-record kernel and one global_load_dwordx4 in frag_local_kernel -- instead of three columns

@@ -1,6 +1,6 @@
 // rsqc_k5.h -- K5, device code only: the kernels of the fragment-size sampler (src/Expression.cpp:482-540) and of the mate pairing
 // of the fragment GC statistics (src/Expression.cpp:459-477).  Included by rsqc_fragsize.hip (which holds the description and
-// the host side) and, unmodified, by the host SIMT emulation of the tests (tests/hostemu/k5_emu.cpp).
+// the host side) and, unmodified, by the host SIMT emulation of the tests (tests/hostemu/k5_emu.cpp; the GC replay: tests/hostemu/gc_emu.cpp).
 #pragma once
 
 namespace rsqc {
@@ -273,7 +273,7 @@ frag_replay_kernel(const FragCandidates c, const uint32_t *off, const uint32_t *
     for (uint32_t k = 0; k < mine; ++k) { sample_file[s_base + at + k] = my_file[k]; sample_size[s_base + at + k] = my_size[k]; }
 }
 
-#if defined(__HIPCC__)   /* (needs the G/C bit helpers of rsqc_device.h, device build only) */
+// (no device-only guard: the G/C bit helpers of rsqc_device.h compile for the emulation too, and tests/hostemu/gc_emu.cpp runs both kernels)
 // src/Expression.cpp:461-476 for every name of the bucket.  Real fragments pile up in a dozen neighbouring bins, i.e. in two
 // cache lines: memory-side atomics on them serialise; the histogram is kept per workgroup in LDS and flushed once.
 __global__ void __launch_bounds__(PB_THREADS)
@@ -370,8 +370,6 @@ gc_replay_big_kernel(const GcCandidates c, const uint32_t *off, const uint32_t *
         __syncthreads();
     }
 }
-
-#endif
 
 // ---- the N smallest file indices among the samples: radix select, one 8-bit digit per pass ---------------------------------
 // counts, per value of the digit at `shift`, the samples whose higher digits equal those of `prefix`
