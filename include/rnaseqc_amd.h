@@ -664,6 +664,42 @@ typedef struct rsqc_junction_table {
 RSQC_API int rsqc_junctions_begin(rsqc_ctx *ctx);
 RSQC_API int rsqc_junctions_end(rsqc_ctx *ctx, rsqc_junction_table *out);
 
+/* ---- per-base coverage track as bedGraph rows (additive to ABI 6) --------------------------------------------------------
+ * Between rsqc_track_begin and the end of the pass every batch that the per-read kernels run also adds its coverage events to a
+ * device-resident difference array (one extra kernel per batch; no other kernel, output or launch changes); rsqc_track_end turns
+ * it into rows on the device, rsqc_track_rows / rsqc_track_text bring windows of them to the host.  The contract, in integers:
+ *   contigs      the n contigs handed to rsqc_track_begin (the header's @SQ entries in order) with their lengths, each at most
+ *                2^31 - 1; names may be NULL (they are needed for text only), at most 255 bytes each.
+ *   population   a record contributes iff (flag & (0x4 | 0x100 | 0x200 | 0x800)) == 0 and its segment's tid is in [0, n): the
+ *                population of rsqc_junctions_*.  Nothing else gates it, the duplicate flag included; two mates are two records.
+ *   walk         p = pos, in 64 bits.  M = X of length L >= 1 cover [p, p + L) and advance p; D and N advance p and cover nothing;
+ *                I S H P do neither; an operation of length 0 does nothing; a wide record's true count is used, clamped to the
+ *                batch's pool.  What lies outside [0, length[tid]) is counted in no depth: its bases are clipped_bases, the
+ *                bases inside are aligned_bases.
+ *   depth        of a position: the number of covering intervals, exact up to 2^32 - 1.
+ *   rows         maximal runs of positions of ONE contig with equal, non-zero depth: (tid, start, end, depth), start 0-based, end
+ *                exclusive, ascending by (tid, start).  The sum of (end - start) * depth is aligned_bases.  The table does not
+ *                depend on the order of the records or on how they are cut into batches.
+ *   text         name<TAB>start<TAB>end<TAB>depth<LF> per row, in decimal; no header or track line; no rows, no bytes.
+ * rsqc_track_begin: after rsqc_set_annotation and before the pass's first submit (RSQC_ERR_ARG otherwise); with rsqc_sort_begin and
+ * rsqc_junctions_begin in any order (under rsqc_sort_begin the events come from the sorted output batches).  It allocates the
+ * array -- 4 bytes per position and contig pad -- or keeps the one of an earlier pass that is large enough, and zeroes it on the
+ * stream; the environment's RSQC_TRACK_MAX_BYTES (default: no bound) makes it return RSQC_ERR_CAPACITY for a larger array.
+ * rsqc_track_end: behind rsqc_finalize or rsqc_finalize_device of that pass; a second call returns the same figures without device
+ * work.  2^32 - 16 rows or more, or an allocation the device refuses, is RSQC_ERR_CAPACITY with the sizes in rsqc_last_error, never
+ * a partial table.  rsqc_track_rows / rsqc_track_text: rows [first, first + n) behind rsqc_track_end; the host arrays are owned by
+ * the context and valid until the next of these two calls; text takes at most 4 194 304 rows a call and needs the names
+ * (RSQC_ERR_ARG without).  rsqc_reset, rsqc_clear_inputs and rsqc_destroy end the mode; rsqc_reset keeps the array's allocation.
+ * Not exchanged by rsqc_reduce_* / rsqc_group_*.                                                                                  */
+typedef struct rsqc_track_info {
+    uint64_t n_rows, population, aligned_bases, clipped_bases, positions;   /* positions: the sum of the lengths            */
+    double events_ms, scan_ms, rows_ms;   /* the per-batch kernels (HIP events); the prefix sum; count + rows (host clocks) */
+} rsqc_track_info;
+RSQC_API int rsqc_track_begin(rsqc_ctx *ctx, int32_t n, const uint64_t *length, const char *const *name /* may be NULL */);
+RSQC_API int rsqc_track_end(rsqc_ctx *ctx, rsqc_track_info *out);
+RSQC_API int rsqc_track_rows(rsqc_ctx *ctx, uint64_t first, uint64_t n, const int32_t **tid, const uint32_t **start, const uint32_t **end, const uint32_t **depth);
+RSQC_API int rsqc_track_text(rsqc_ctx *ctx, uint64_t first, uint64_t n, const char **text, uint64_t *bytes);
+
 RSQC_API const char *rsqc_strerror(int code);
 RSQC_API const char *rsqc_last_error(rsqc_ctx *ctx);
 RSQC_API const char *rsqc_counter_name(int counter);   /* the reference's Metrics key  */

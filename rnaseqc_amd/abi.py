@@ -196,6 +196,11 @@ class JunctionTable(C.Structure):
                 ("extract_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double)]
 
 
+class TrackInfo(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("population", C.c_uint64), ("aligned_bases", C.c_uint64), ("clipped_bases", C.c_uint64), ("positions", C.c_uint64),
+                ("events_ms", C.c_double), ("scan_ms", C.c_double), ("rows_ms", C.c_double)]
+
+
 def ptr(a: np.ndarray | None):
     """numpy array -> void* (None -> NULL).  The caller keeps `a` alive."""
     if a is None:

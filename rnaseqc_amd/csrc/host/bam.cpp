@@ -475,6 +475,7 @@ bool BamReader::open(const std::string &path) {
             const uint32_t l_name = le32(buf_.data() + pos_);
             if (!fill(8 + (size_t)l_name)) return false;
             names_.emplace_back((const char *)buf_.data() + pos_ + 4, l_name ? l_name - 1 : 0);
+            lengths_.push_back(le32(buf_.data() + pos_ + 4 + l_name));
             pos_ += 8 + l_name;
         }
     } catch (std::exception &) { return false; }

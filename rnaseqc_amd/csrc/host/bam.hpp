@@ -124,6 +124,7 @@ class BamReader {
 public:
     bool open(const std::string &path);                 // false: cannot open / not a BAM
     const std::vector<std::string> &contigs() const { return names_; }
+    const std::vector<uint64_t> &contig_lengths() const { return lengths_; }     // l_ref of the header, in the same order
     // tags: the chimeric tag (2 chars) and up to RSQC_MAX_FILTER_TAGS filter tags
     void set_tags(const std::string &chimeric, const std::vector<std::string> &filters);
     // appends up to max_records records to `out`; returns the number appended (0 at EOF)
@@ -177,6 +178,7 @@ private:
     std::mutex mu_;
     std::condition_variable cv_;
     std::vector<std::string> names_;
+    std::vector<uint64_t> lengths_;
     std::string ch_tag_ = "ch";
     std::vector<std::string> filter_tags_;
     uint64_t n_read_ = 0;

@@ -34,7 +34,7 @@ public:
     bool open(const std::string &path);
     // Virtual offset (coffset << 16 | uoffset) of the first alignment record: inflates the header's blocks on the host.
     // names (may be null): the reference sequence names of the header.  Throws std::runtime_error on a file that is not a BAM.
-    uint64_t first_record_voffset(std::vector<std::string> *names = nullptr);
+    uint64_t first_record_voffset(std::vector<std::string> *names = nullptr, std::vector<uint64_t> *lengths = nullptr);   // (names and l_ref of the header's references)
     // page-locks the three chunk buffers now (else: by the read-ahead thread when it first fills them -- page-locking takes
     // the HIP runtime's lock, and the thread that feeds the GPU stalls behind it)
     // max_out (0 = unknown): the inflated bytes a call holds at most -- with it the buffers are sized for what that takes in THIS file

@@ -52,6 +52,7 @@ struct Options {
     std::vector<std::string> tags;
     int gpus = 0;                      // --gpus (extension): GPUs to shard the BAM over by contig; 0 = RSQC_GPUS or 1
     std::string bam_list; bool has_bam_list = false;   // --bam-list (extension): a cohort, the positionals are `gtf output`
+    bool bedgraph = false;             // --bedgraph (extension): the per-base coverage track, <sample>.coverage.bedgraph (rsqc_track_begin / _end / _text)
     bool junctions = false;            // --junctions (extension): reads per splice junction, <sample>.junctions.tsv (rsqc_junctions_begin / rsqc_junctions_end)
     bool sort = false;                 // --sort (extension): input in any order, put in coordinate order on the GPU (rsqc_sort_begin / rsqc_sort_end)
 };
@@ -87,7 +88,8 @@ void usage(std::ostream &o) {
          "      --gpus=[N]                        (extension) Shard the BAM by contig over N GPUs of this node; needs [bam].bai. Default: 1\n"
          "      --bam-list=[FILE]                 (extension) A cohort on one GPU: FILE lists one input per line, path[<TAB>sample]; the positionals are [gtf] [output]\n"
          "      --sort                            (extension) Accept input in any order: the records are put in coordinate order on the GPU before they are counted\n"
-         "      --junctions                       (extension) Count reads per splice junction on the GPU and write [sample].junctions.tsv (one GPU)\n";
+         "      --junctions                       (extension) Count reads per splice junction on the GPU and write [sample].junctions.tsv (one GPU)\n"
+         "      --bedgraph                        (extension) Build the per-base coverage track on the GPU and write [sample].coverage.bedgraph (one GPU; needs LN in the header)\n";
 }
 
 long to_long(const std::string &flag, const std::string &v) {
@@ -168,6 +170,7 @@ Options parse(int argc, char **argv) {
         else if (name == "bam-list") { o.bam_list = need(); o.has_bam_list = true; }
         else if (name == "sort") o.sort = true;
         else if (name == "junctions") o.junctions = true;
+        else if (name == "bedgraph") o.bedgraph = true;
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
         else if (name == "detection-threshold") o.detection = to_ulong(name, need());
         else throw ParseError("Flag could not be matched: " + name);
@@ -402,6 +405,7 @@ struct Input {
     bool is_stream = false;                           // a FIFO / stdin: streamed by the host (the block feeder needs pread)
     InputFormat fmt = InputFormat::Unknown;
     std::vector<std::string> contigs;                 // the header's reference names, in order
+    std::vector<uint64_t> lengths;                    // ... and their lengths (@SQ LN / l_ref; 0: absent)
     uint64_t first_voff = 0, file_size = 0;           // BAM for the device decode: virtual offset of the first record
     std::unique_ptr<SamTextFeeder> stream_feed;       // SAM text from a stream: holds the bytes that were read to sniff it
     std::unique_ptr<BamReader> reader;                // BAM decoded on the host (RSQC_DECODE=host, or a stream)
@@ -460,17 +464,17 @@ std::unique_ptr<Input> open_input(const std::string &path, const Options &o) {
                 if (complete || hd.size() < want) break;
             }
         } else if (!read_sam_header(path, hdr)) { in->error = unable; return in; }
-        in->contigs = hdr.names;
+        in->contigs = hdr.names; in->lengths = hdr.lengths;
     } else if (device_decode_wanted(in->is_stream)) {
         BgzfFeeder probe;
         if (!probe.open(path)) { in->error = unable; return in; }
-        try { in->first_voff = probe.first_record_voffset(&in->contigs); }
+        try { in->first_voff = probe.first_record_voffset(&in->contigs, &in->lengths); }
         catch (std::exception &) { in->error = unable; return in; }
     } else {
         in->reader.reset(new BamReader());
         if (!in->reader->open(reader_path)) { in->error = unable; in->reader.reset(); return in; }
         in->reader->set_tags(o.chimeric_tag, o.tags);
-        in->contigs = in->reader->contigs();
+        in->contigs = in->reader->contigs(); in->lengths = in->reader->contig_lengths();
     }
     return in;
 }
@@ -629,6 +633,33 @@ struct JunctionCopy {
     }
 };
 
+// --bedgraph: <output>/<sample>.coverage.bedgraph from the rows on the device, a window of text at a time: the next window is
+// formatted (rsqc_track_text) while a second thread writes the one before.  Returns an RSQC code; io_failed: the file could not be written
+int write_bedgraph(rsqc_ctx *gpu, const std::string &path, uint64_t n_rows, uint64_t &bytes_out, double &text_seconds, bool &io_failed) {
+    const uint64_t window = 4194304;                   // (the most rsqc_track_text takes)
+    const Clock::time_point t0 = Clock::now();
+    std::ofstream f(path, std::ios::binary | std::ios::trunc);
+    io_failed = !f.is_open(); bytes_out = 0;
+    std::vector<char> buf[2];
+    std::future<void> writing;
+    int cur = 0, rc = RSQC_OK;
+    for (uint64_t first = 0; first < n_rows && rc == RSQC_OK && !io_failed; first += window) {
+        const char *text = nullptr; uint64_t bytes = 0;
+        if ((rc = rsqc_track_text(gpu, first, std::min(window, n_rows - first), &text, &bytes)) != RSQC_OK) break;
+        buf[cur].assign(text, text + bytes);           // (the context's window ends with the next call)
+        if (writing.valid()) writing.get();
+        if (!f.good()) { io_failed = true; break; }
+        const std::vector<char> *b = &buf[cur];
+        writing = std::async(std::launch::async, [&f, b] { f.write(b->data(), (std::streamsize)b->size()); });
+        bytes_out += bytes; cur ^= 1;
+    }
+    if (writing.valid()) writing.get();
+    f.close();
+    if (!f.good()) io_failed = true;
+    text_seconds = seconds_between(t0, Clock::now());
+    return rc;
+}
+
 int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, const std::string &out_dir, SampleRow &row) {
     using std::cerr; using std::cout; using std::endl;
     std::unique_ptr<Input> opened = sample.opened.valid() ? sample.opened.get() : open_input(sample.path, o);
@@ -643,6 +674,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     if (sam_input && o.verbosity > 1) cout << "Input: " << input_format_name(in.fmt) << " (" << bam_contigs.size() << " @SQ lines), parsed on the GPU" << endl;
     if (o.verbosity > 1) cout << "Checking bam header..." << endl;
     if (!shares_contigs(S, ann, bam_contigs)) { cerr << S.prefix << "BAM file shares no contigs with GTF" << endl; return 11; }
+    if (o.bedgraph)                                    // the track needs every contig's length
+        for (size_t k = 0; k < bam_contigs.size(); ++k)
+            if (k >= in.lengths.size() || in.lengths[k] == 0) { cerr << S.prefix << "--bedgraph needs the length (LN) of every contig in the header: none for " << bam_contigs[k] << endl; return 10; }
     const bool same_header = S.flattened && bam_contigs == S.contigs;
     if (!same_header) flatten_for(S, ann, bam_contigs);
     const int n_ref_bam = (int)bam_contigs.size();
@@ -750,6 +784,12 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     if (o.sort && (rc = rsqc_sort_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --junctions: every batch the per-read kernels run leaves its junction instances on the device (under --sort: the sorted batches)
     if (o.junctions && (rc = rsqc_junctions_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    // --bedgraph: and its coverage events, in a difference array over the header's contigs (kept by the context while it is large enough)
+    if (o.bedgraph) {
+        std::vector<const char *> track_names;
+        for (auto &nm : bam_contigs) track_names.push_back(nm.c_str());
+        if ((rc = rsqc_track_begin(gpu, n_ref_bam, in.lengths.data(), track_names.data())) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    }
     if (sam_input) {
         // ---- SAM text: the host reads the file (plain) or frames its BGZF blocks, the device does the rest
         rsqc_decode_info di{};
@@ -842,6 +882,8 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     if (rc == RSQC_OK) rc = rsqc_finalize(gpu, &res);
     rsqc_junction_table junctions{};
     if (o.junctions && rc == RSQC_OK) rc = rsqc_junctions_end(gpu, &junctions);       // (ordered and reduced inside the timed window: the price of the flag)
+    rsqc_track_info track{};
+    if (o.bedgraph && rc == RSQC_OK) rc = rsqc_track_end(gpu, &track);                // (scan and rows inside the timed window as well)
     S.t_loop1 = Clock::now();
     if (rc == RSQC_ERR_BAD_CIGAR) throw std::invalid_argument("Unrecognized Cigar Op ");
     if (rc == RSQC_ERR_EMPTY_MEDIAN) throw std::range_error("Cannot compute median of an empty list");
@@ -857,6 +899,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (o.junctions)
             cout << "Junctions: population " << junctions.population << ", instances " << junctions.instances << ", rows " << junctions.n << ", extract_ms " << junctions.extract_ms
                  << ", sort_ms " << junctions.sort_ms << ", reduce_ms " << junctions.reduce_ms << endl;
+        if (o.bedgraph)
+            cout << "Track: population " << track.population << ", aligned_bases " << track.aligned_bases << ", clipped_bases " << track.clipped_bases << ", rows " << track.n_rows
+                 << ", events_ms " << track.events_ms << ", scan_ms " << track.scan_ms << ", rows_ms " << track.rows_ms << endl;
         cout << "Estimating library complexity..." << endl;
         cout << "Generating report" << endl;
     }
@@ -866,6 +911,14 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     cfg.filter_tags = o.tags;
     const std::string junctions_path = out_dir + "/" + sample.name + ".junctions.tsv";
     if (o.junctions && !S.junction_index.built) S.junction_index.build(ann);
+    if (o.bedgraph) {
+        // the track's text comes from the context window by window: written here, on the report path, before the context's next reset
+        uint64_t bytes = 0; double secs = 0; bool io_failed = false;
+        rc = write_bedgraph(gpu, out_dir + "/" + sample.name + ".coverage.bedgraph", track.n_rows, bytes, secs, io_failed);
+        if (rc != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+        if (io_failed) { cerr << S.prefix << "Filesystem error:  cannot write " << out_dir << "/" << sample.name << ".coverage.bedgraph" << endl; return 8; }
+        if (o.verbosity) cout << "Track text: rows " << track.n_rows << ", bytes " << bytes << ", seconds " << secs << endl;
+    }
     if (!S.async_reports) {
         S.t_rep0 = Clock::now();
         write_reports(cfg, ann, res, visit);
@@ -1165,6 +1218,12 @@ int main(int argc, char **argv) {
             bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
             if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
             if (many_gpus) throw ValidationError("--sort runs on one GPU (--gpus, RSQC_GPUS and RSQC_GPU_LIST shard a coordinate-sorted, indexed BAM)");
+        }
+        if (o.bedgraph) {
+            // one difference array per context: the arrays of shards would need adding up, and that path is not built
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--bedgraph runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
         }
         if (o.junctions) {
             // one table per context: the per-contig tables of shards would only need concatenating, but that path is not built

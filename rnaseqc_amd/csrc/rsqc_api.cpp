@@ -118,6 +118,7 @@ void rsqc_destroy(rsqc_ctx *c) {
     }
     sort_drop(c);
     junction_drop(c, true);
+    track_drop(c, true);
     for (auto &b : c->parked) b.release();
     free_sort_scratch(c->gc_scratch); free_sort_scratch(c->frag_scratch);
     c->d_ref_bits.release(); c->d_ref_off.release(); c->d_ref_len.release(); c->d_gc_bins.release(); c->d_exon_gc.release();
@@ -360,6 +361,7 @@ int rsqc_reset(rsqc_ctx *c) {
     RSQC_TRACE("reset: enter");
     if (c->sort.active || c->sort.core.p) sort_drop(c);
     junction_drop(c, false);                           // (the columns stay for the next pass)
+    track_drop(c, false);                              // (and so does the difference array)
     const int rc = zero_accumulators(c);
     RSQC_TRACE("reset: enqueued");
     return rc;
@@ -378,6 +380,7 @@ int rsqc_clear_inputs(rsqc_ctx *c) {
     free_parked(c);
     sort_drop(c);
     junction_drop(c, false);
+    track_drop(c, false);
     // an open decode stream is dropped with its carried-over bytes; its window buffers stay
     c->dec.active = false; c->dec.pending = false; c->dec.tail = 0;
     // the batches in flight hand their buffers back to the pools; what the pass has emitted so far goes with the arenas

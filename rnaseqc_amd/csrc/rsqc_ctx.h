@@ -148,6 +148,20 @@ struct JunctionState {
     rsqc_junction_table table{};
 };
 
+// --bedgraph (rsqc_track_begin / rsqc_track_end / rsqc_track_rows / rsqc_track_text, rsqc_track_api.cpp): the difference array of
+// the pass (4 bytes per reference position, kept across rsqc_reset), the rows on the device (16 bytes each), one window on the host
+struct TrackState {
+    bool active = false, done = false, have_names = false, merge_later = false;
+    int32_t n = 0;
+    uint64_t total = 0;                                // slots of the difference array without the scan's extra one: sum of (length + 1)
+    DevBuf diff, off, length, sums, names, name_off, counts, chunk_sum, totals, rows, linelen, text;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;   // around every batch's events kernel
+    rsqc_track_info info{};
+    std::vector<int32_t> h_tid;                        // the window of the last rsqc_track_rows
+    std::vector<uint32_t> h_start, h_end, h_depth;
+    char *h_text = nullptr; size_t h_text_cap = 0;     // page-locked: the window of the last rsqc_track_text
+};
+
 }  // namespace rsqc
 using namespace rsqc;            // (every unit that sees this header is host code of the library)
 
@@ -241,6 +255,7 @@ struct rsqc_ctx {
     DecodeState dec;
     SortState sort;
     JunctionState junc;
+    TrackState track;
 
     // host results
     std::vector<uint64_t> h_fcount;
@@ -278,6 +293,9 @@ void sort_drop(rsqc_ctx *c);                   // leaves the collecting mode and
 // --junctions: the batch's instances appended to the collection, on the main stream (rsqc_junction_api.cpp)
 int junction_extract(rsqc_ctx *c, const UploadedBatch *u, const DevBatch &d);
 void junction_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the instances
+// --bedgraph: the batch's coverage events added to the difference array, on the main stream (rsqc_track_api.cpp)
+int track_events(rsqc_ctx *c, const UploadedBatch *u, const DevBatch &d);
+void track_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forgets the track
 
 template <class T>
 int upload(rsqc_ctx *c, std::vector<DevBuf> &owner, const T *host, size_t n, const T **out, bool from_pool = false) {

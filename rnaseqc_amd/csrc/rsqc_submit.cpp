@@ -356,6 +356,8 @@ int run_batch(rsqc_ctx *c, UploadedBatch *u) {
     }
     // --junctions: the batch's splice-junction instances, in front of the event that retires the batch (its buffers are read)
     if (c->junc.active) { if (int rc2 = junction_extract(c, u, d)) return rc2; }
+    // --bedgraph: the batch's coverage events, likewise
+    if (c->track.active) { if (int rc2 = track_events(c, u, d)) return rc2; }
     // the batch's counts, for its retirement: page-locked mirrors + an event that tells when they are valid.  The copy of the
     // pair counts rides on a side stream: a copy between two kernels of the main stream costs ~40 us of queue hand-over there
     // (profiles/r4_step_timeline.txt), and nothing on the main stream reads what it brings

@@ -75,6 +75,10 @@ def load_library():
         lib.rsqc_sort_end.argtypes = [vp, C.POINTER(abi.SortInfo)]
         lib.rsqc_junctions_begin.argtypes = [vp]
         lib.rsqc_junctions_end.argtypes = [vp, C.POINTER(abi.JunctionTable)]
+        lib.rsqc_track_begin.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_char_p)]
+        lib.rsqc_track_end.argtypes = [vp, C.POINTER(abi.TrackInfo)]
+        lib.rsqc_track_rows.argtypes = [vp, C.c_uint64, C.c_uint64] + [C.POINTER(vp)] * 4
+        lib.rsqc_track_text.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
         _lib = lib
     return _lib
 
@@ -87,6 +91,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_last_error", "rsqc_counter_name", "rsqc_version", "rsqc_qname_hash", "rsqc_qname_hash2",
     "rsqc_decode_begin", "rsqc_decode_submit", "rsqc_decode_end", "rsqc_decode_begin_sam", "rsqc_decode_submit_text",
     "rsqc_sort_begin", "rsqc_sort_end", "rsqc_junctions_begin", "rsqc_junctions_end",
+    "rsqc_track_begin", "rsqc_track_end", "rsqc_track_rows", "rsqc_track_text",
 ]
 
 
@@ -257,6 +262,35 @@ class Engine:
         out.update({f: abi._view(getattr(t, f), n, np.uint32) for f in ("reads", "hq_reads", "max_overhang")})
         out.update(n=n, instances=int(t.instances), population=int(t.population), extract_ms=t.extract_ms, sort_ms=t.sort_ms, reduce_ms=t.reduce_ms)
         return out
+
+    # ---- per-base coverage track (rsqc_track_*) ---------------------------------------------------------------------
+    def track_begin(self, lengths, names=None):
+        """From here to the end of the pass every batch that is run also adds its coverage events to a difference array over the
+        contigs of `lengths`; `names` (needed for track_text only) are the contigs' names."""
+        lens = np.ascontiguousarray([int(x) for x in lengths], dtype=np.uint64)
+        arr = None
+        if names is not None:
+            assert len(names) == len(lens)
+            arr = (C.c_char_p * max(len(lens), 1))(*[n.encode() if isinstance(n, str) else n for n in names])
+        self._check(self._l.rsqc_track_begin(self._h, len(lens), abi.ptr(lens), arr))
+
+    def track_end(self) -> dict:
+        """After finalize() / finalize_device(): the rows are built on the device; the fields of rsqc_track_info."""
+        info = abi.TrackInfo()
+        self._check(self._l.rsqc_track_end(self._h, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in abi.TrackInfo._fields_}
+
+    def track_rows(self, first, n) -> dict:
+        """Rows [first, first + n) as numpy arrays (copies): tid (int32), start, end, depth (uint32)."""
+        p = [C.c_void_p() for _ in range(4)]
+        self._check(self._l.rsqc_track_rows(self._h, int(first), int(n), *[C.byref(x) for x in p]))
+        return {f: abi._view(x.value, int(n), dt).copy() for f, x, dt in zip(("tid", "start", "end", "depth"), p, (np.int32, np.uint32, np.uint32, np.uint32))}
+
+    def track_text(self, first, n) -> bytes:
+        """Rows [first, first + n) as bedGraph text, formatted on the device."""
+        p, nbytes = C.c_void_p(), C.c_uint64()
+        self._check(self._l.rsqc_track_text(self._h, int(first), int(n), C.byref(p), C.byref(nbytes)))
+        return C.string_at(p.value, nbytes.value) if nbytes.value else b""
 
     def read_device(self, ptr, count, dtype):
         """count items of dtype from a device pointer of this context (tests): hipMemcpy of the HIP runtime the library itself is
