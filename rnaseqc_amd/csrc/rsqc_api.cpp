@@ -199,15 +199,10 @@ int rsqc_set_annotation(rsqc_ctx *c, const rsqc_annotation *a, const uint8_t *ow
     std::stable_sort(gene_order.begin(), gene_order.begin() + L, [&](uint32_t x, uint32_t y) { return gene_coding[x] > gene_coding[y]; });
     UPV(c->d_gene_order, gene_order);
     // workgroup size classes of the end-of-file coverage stage (rsqc_kernels.hip, K3)
-    c->k3_large = c->k3_medium = c->k3_xlarge = c->k3_le6144 = c->k3_le3072 = c->k3_le2048 = c->k3_le1024 = 0;
-    for (int k = 0; k < L; ++k) {
-        const uint32_t len = gene_coding[gene_order[(size_t)k]];
-        if (len > (uint32_t)RSQC_K3_MEDIUM_MAX) c->k3_large++; else if (len > (uint32_t)RSQC_K3_SMALL_MAX) c->k3_medium++;
-        if (len > (uint32_t)RSQC_K3_LARGE2_LDS16) c->k3_xlarge++;
-        if (len <= 6144u) c->k3_le6144++;
-        if (len <= 3072u) c->k3_le3072++;
-        if (len <= 2048u) c->k3_le2048++;
-        if (len <= 1024u) c->k3_le1024++;
+    {
+        const K3Counts k3 = k3_count_classes(gene_coding.data(), gene_order.data(), (uint32_t)L);      // (rsqc_k3_plan.h)
+        c->k3_large = k3.n_large; c->k3_medium = k3.n_medium; c->k3_xlarge = k3.n_xlarge;
+        c->k3_le6144 = k3.n_le6144; c->k3_le3072 = k3.n_le3072; c->k3_le2048 = k3.n_le2048; c->k3_le1024 = k3.n_le1024;
     }
 #undef UPV
 #undef UPA

@@ -11,14 +11,7 @@
 #define RSQC_K1_THREADS 256
 #define RSQC_MAX_BIAS_WINDOW 1024
 #define RSQC_K3_THREADS 1024
-// coding-length classes of the end-of-file coverage stage: one wave / 256 threads with the vector in LDS, 1024 threads in memory
-#ifndef RSQC_K3_SMALL_MAX
-#define RSQC_K3_SMALL_MAX 4096
-#endif
-#define RSQC_K3_MEDIUM_MAX 12288
-#define RSQC_K3_LARGE_LDS16 73000      /* bases a 1024-thread workgroup keeps in LDS as 16-bit depths (146 KB of the CU's 160 KB) */
-#define RSQC_K3_LARGE2_LDS16 32768     /* ... the shorter genes of that class: 64 KB */
-#define RSQC_K3_MAX_EXONS 1024
+#include "rsqc_k3_plan.h"        /* the coding-length classes of the end-of-file coverage stage (RSQC_K3_*) and its launch plan */
 
 namespace rsqc {
 

@@ -164,7 +164,7 @@ _K3SO = os.path.join(_HERE, "libk3emu.so")
 def build_k3():
     csrc = os.path.join(_ROOT, "rnaseqc_amd", "csrc")
     srcs = [os.path.join(_HERE, "k3_emu.cpp"), os.path.join(_HERE, "wavemu.h")] + \
-           [os.path.join(csrc, f) for f in ("rsqc_k3.h", "rsqc_wave.h", "rsqc_device.h", "rsqc_read.h", "rsqc_index.h")]
+           [os.path.join(csrc, f) for f in ("rsqc_k3.h", "rsqc_k3_plan.h", "rsqc_wave.h", "rsqc_device.h", "rsqc_read.h", "rsqc_index.h")]
     if not os.path.exists(_K3SO) or any(os.path.getmtime(_K3SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-unused-function",
                                "-Wno-unused-variable", srcs[0], "-o", _K3SO])
@@ -173,7 +173,9 @@ def build_k3():
 
 def run_k3(params, ann, cov_diff, gene_reads, force=0):
     """The end-of-file coverage KERNEL (rsqc_k3.h) on the 64-lane fiber emulation: from the difference array and the gene counts
-    of a pass (hostemu.run(..., want_cov=True)) to per-gene mean / std / CV, per-exon CV and the bias accumulators."""
+    of a pass (hostemu.run(..., want_cov=True)) to per-gene mean / std / CV, per-exon CV and the bias accumulators.  The launches are
+    the library's own plan (rsqc_k3_plan.h); `launches`: genes per launch, in launch order; `classes`: genes per workgroup class
+    (1024 threads / 146 KB, 1024 / 64 KB, 256, one wave)."""
     lib = C.CDLL(build_k3())
     a = ann.to_struct()
     o = Out()
@@ -181,14 +183,55 @@ def run_k3(params, ann, cov_diff, gene_reads, force=0):
     o.gene_cov_mean = np.zeros(G, np.float64); o.gene_cov_std = np.zeros(G, np.float64); o.gene_cov_cv = np.zeros(G, np.float64)
     o.gene_cov_valid = np.zeros(G, np.uint8); o.exon_cv = np.zeros(E, np.float64); o.exon_cv_valid = np.zeros(E, np.uint8)
     o.bias_three = np.zeros(G, np.uint64); o.bias_five = np.zeros(G, np.uint64)
-    stats = np.zeros(4, np.uint64)
+    stats = np.zeros(K3_LAUNCHES, np.uint64)
     cov = np.ascontiguousarray(cov_diff, np.uint32); gr = np.ascontiguousarray(gene_reads, np.uint64)
     rc = lib.k3emu_run(C.byref(params), C.byref(a), abi.ptr(cov), abi.ptr(gr), C.c_int(force), abi.ptr(o.gene_cov_mean), abi.ptr(o.gene_cov_std),
                        abi.ptr(o.gene_cov_cv), abi.ptr(o.gene_cov_valid), abi.ptr(o.exon_cv), abi.ptr(o.exon_cv_valid),
                        abi.ptr(o.bias_three), abi.ptr(o.bias_five), abi.ptr(stats))
     o.rc = rc
-    o.classes = [int(x) for x in stats]
+    o.launches = [int(x) for x in stats]
+    o.classes = [o.launches[0], o.launches[3], o.launches[1] + o.launches[2], sum(o.launches[4:])]
     return o
+
+
+K3_LAUNCHES = 8
+K3_PLAN_COLUMNS = ("threads", "cov_bits", "cap", "count", "first", "stream")
+K3_COUNT_NAMES = ("n_large", "n_medium", "n_xlarge", "n_le6144", "n_le3072", "n_le2048", "n_le1024")
+
+
+def _plan_rows(out):
+    return [dict(zip(K3_PLAN_COLUMNS, (int(x) for x in out[k * 6:k * 6 + 6]))) for k in range(K3_LAUNCHES)]
+
+
+def k3_plan(n, n_large, n_medium, n_xlarge, n_le6144, n_le3072, n_le2048, n_le1024):
+    """The library's launch plan of the coverage stage (rsqc_k3_plan.h: k3_plan) from class counts as given, no kernel run: eight dicts
+    of K3_PLAN_COLUMNS in launch order."""
+    lib = C.CDLL(build_k3())
+    lib.k3emu_plan.argtypes = [C.c_uint32] * 8 + [C.c_void_p]
+    lib.k3emu_plan.restype = None
+    out = np.zeros(K3_LAUNCHES * 6, np.uint32)
+    lib.k3emu_plan(n, n_large, n_medium, n_xlarge, n_le6144, n_le3072, n_le2048, n_le1024, out.ctypes.data)
+    return _plan_rows(out)
+
+
+def k3_plan_many(lengths, ns, force=0, delta=None):
+    """... from coding lengths, the way the emulation (and, for force=0, the library) gets there, for many length vectors at once: row r
+    of `lengths` (m x width) holds ns[r] lengths; they are sorted longest first, the classes counted by k3_count_classes, `force` applied,
+    `delta` (m x 7, K3_COUNT_NAMES order) added to the counts, then k3_plan.  Returns (counts m x 7, plans m x 8 x 6 in K3_PLAN_COLUMNS
+    order, sorted lengths m x width), all int64."""
+    lib = C.CDLL(build_k3())
+    lib.k3emu_plan_many.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.k3emu_plan_many.restype = None
+    ln = np.ascontiguousarray(lengths, np.uint32)
+    m, width = ln.shape
+    nn = np.ascontiguousarray(ns, np.uint32)
+    assert nn.shape == (m,) and (m == 0 or int(nn.max()) <= width)
+    dl = None if delta is None else np.ascontiguousarray(delta, np.int32)
+    assert dl is None or dl.shape == (m, 7)
+    counts = np.zeros((m, 7), np.uint32); out = np.zeros((m, K3_LAUNCHES, 6), np.uint32); srt = np.zeros((m, width), np.uint32)
+    lib.k3emu_plan_many(ln.ctypes.data, nn.ctypes.data, m, width, int(force), None if dl is None else dl.ctypes.data, counts.ctypes.data,
+                        out.ctypes.data, srt.ctypes.data)
+    return counts.astype(np.int64), out.astype(np.int64), srt.astype(np.int64)
 
 
 _K5SO = os.path.join(_HERE, "libk5emu.so")
