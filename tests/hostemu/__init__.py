@@ -158,6 +158,45 @@ def run_k4(seed, n_genes, n_chunks, n_names, hot_reads, arena=False, wide=False)
     return rc, dict(zip(("pairs", "kept", "partitions", "fuller", "distinct", "chunk_cap"), (int(x) for x in st)))
 
 
+K4_PART_READS, K4_SUB_CAP, K4_PART_SLOTS = 1024, 2048, 4096       # rsqc_device.h
+
+
+def k4_bounds(n_pairs, n_genes):
+    """(parts_bound, keys_bound) of rsqc_finalize.cpp from the host's pair bound."""
+    parts = n_pairs // K4_PART_READS + n_genes + 1
+    keys = 2 * n_pairs + K4_SUB_CAP * min(parts, n_pairs // K4_PART_READS + 1) + 16 * n_genes + 16
+    return parts, keys
+
+
+def run_k4_pairs(gene, key, h2, n_genes, counts, chunk_cap, slow_cap, sharers, grid_small, grid_large, seed=0):
+    """The fragment-counting KERNELS (rsqc_k4.h) over pairs laid out by the caller (k4_emu.cpp: k4emu_run_pairs).  counts: pairs per
+    chunk, then the pairs of the dense region (one entry alone: the dense form); seed: wavemu.h's seeded schedule (0: round-robin).
+    Returns an Out: rc, error, gene_frag[G], part_first[G + 1], ginfo[G, 4], part_info[n_parts, 4], cursor[n_parts] (the fills
+    frag_local left), full_list[full_n] sorted, full_n."""
+    lib = C.CDLL(build_k4())
+    lib.k4emu_run_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64] + [C.c_void_p] * 8
+    gene = np.ascontiguousarray(gene, np.uint32); key = np.ascontiguousarray(key, np.uint64); h2 = np.ascontiguousarray(h2, np.uint32)
+    cnt = np.ascontiguousarray(counts, np.uint32)
+    n = len(gene)
+    assert len(key) == n and len(h2) == n and len(cnt) >= 1
+    pb, kb = k4_bounds(n, n_genes)
+    o = Out()
+    err = C.c_int(0); full_n = C.c_uint32(0)
+    o.gene_frag = np.zeros(n_genes, np.uint64); part_first = np.zeros(n_genes + 1, np.uint32); ginfo = np.zeros((n_genes, 4), np.uint32)
+    part_info = np.zeros((pb, 4), np.uint32); cursor = np.zeros(pb, np.uint32); full_list = np.zeros(pb, np.uint32)
+    o.rc = lib.k4emu_run_pairs(gene.ctypes.data, key.ctypes.data, h2.ctypes.data, n, n_genes, len(cnt) - 1, chunk_cap, cnt.ctypes.data, slow_cap,
+                               sharers, grid_small, grid_large, int(seed), pb, kb, C.addressof(err), o.gene_frag.ctypes.data, part_first.ctypes.data,
+                               ginfo.ctypes.data, part_info.ctypes.data, cursor.ctypes.data, full_list.ctypes.data, C.addressof(full_n))
+    o.error = err.value; o.full_n = full_n.value
+    o.part_first = part_first.astype(np.int64); o.ginfo = ginfo.astype(np.int64)
+    o.n_parts = int(part_first[n_genes]) if o.rc != -1004 else 0
+    np_ = min(o.n_parts, pb)
+    o.part_info = part_info[:np_].astype(np.int64); o.cursor = cursor[:np_].astype(np.int64)
+    o.full_list = np.sort(full_list[:min(o.full_n, pb)].astype(np.int64))
+    return o
+
+
 _K3SO = os.path.join(_HERE, "libk3emu.so")
 
 

@@ -136,3 +136,91 @@ int k4emu_run(uint64_t seed, int n_genes, int n_chunks, int n_names, int hot_rea
     for (uint32_t g = 0; g < G; ++g) if (gene_frag[g] != (unsigned long long)names[g].size()) return 1 + (int)g;
     return 0;
 }
+
+// k4emu_run_pairs: the same kernels over pairs the CALLER lays out (tests/k4_cases.py: named cases at the edges of the constants).
+// gene/key/h2[n_pairs] in stream order: counts[c] pairs go to chunk c (c < n_chunks, chunk_cap entries each), the last counts[n_chunks] to the
+// dense region of slow_cap entries behind them (n_chunks = 0: the dense form of retired batches); `sharers` workgroups share that region;
+// grid_small / grid_large: the two frag_count launches; sched_seed: wavemu::set_seed (0: round-robin).  Arrays are sized the way
+// rsqc_finalize.cpp sizes them (the caller passes parts_bound and keys_bound computed by the same formulas) and poisoned; frag_count runs
+// whatever frag_local reported, as on the device.  Unused pair slots name gene n_genes, whose row is all zero (capacity 0): a kernel that
+// reads one reports RSQC_ERR_CAPACITY instead of leaving the arrays.
+// Out: error word, gene_frag[G], part_first[G + 1], ginfo[G], part_info[parts_bound], cursor[parts_bound] as frag_local left it,
+// full_list[parts_bound], full_n.  Returns 0, or -1000 (layout beyond its bounds / full_n not cleared), -1003 (a list entry outside every
+// partition's filled range was written), -1004 (bad arguments).
+extern "C" __attribute__((visibility("default")))
+int k4emu_run_pairs(const uint32_t *gene, const uint64_t *key, const uint32_t *h2, uint64_t n_pairs, uint32_t n_genes,
+                    uint32_t n_chunks, uint32_t chunk_cap, const uint32_t *counts, uint32_t slow_cap, uint32_t sharers,
+                    uint32_t grid_small, uint32_t grid_large, uint64_t sched_seed, uint64_t parts_bound, uint64_t keys_bound,
+                    int *error_out, unsigned long long *gene_frag, uint32_t *part_first_out, uint32_t *ginfo_out, uint32_t *part_info_out,
+                    uint32_t *cursor_out, uint32_t *full_list_out, uint32_t *full_n_out) {
+    const uint32_t G = n_genes;
+    if (G == 0 || sharers == 0 || grid_small == 0 || grid_large == 0) return -1004;
+    uint64_t placed = 0;
+    for (uint32_t c = 0; c < n_chunks; ++c) { if (counts[c] > chunk_cap) return -1004; placed += counts[c]; }
+    if (counts[n_chunks] > slow_cap || placed + counts[n_chunks] != n_pairs) return -1004;
+    std::vector<unsigned long long> gene_reads(G, 0ull);
+    for (uint64_t i = 0; i < n_pairs; ++i) { if (gene[i] >= G) return -1004; gene_reads[gene[i]]++; }
+
+    const uint32_t lay_blocks = (G + 1023u) / 1024u;
+    std::vector<uint4> ginfo(G + 1, uint4{0xDEADBEEFu, 0xDEADBEEFu, 0xDEADBEEFu, 0xDEADBEEFu}), part_info(parts_bound, uint4{0xDEADBEEFu, 0xDEADBEEFu, 0xDEADBEEFu, 0xDEADBEEFu});
+    ginfo[G] = uint4{0u, 0u, 0u, 0u};                                         // (the row of the unused pair slots)
+    std::vector<uint32_t> part_first(G + 2, 0xDEADBEEFu), cursor(parts_bound, 0xDEADBEEFu), full_list(parts_bound, 0xDEADBEEFu), blk_parts(lay_blocks, 0xDEADBEEFu);
+    std::vector<unsigned long long> blk_space(lay_blocks, 0xDEADBEEFDEADBEEFull);
+    const FragKey poison{0xABABABABu, 0xABABABABu, 0xCDCDCDCDu};
+    std::vector<FragKey> list(keys_bound, poison);
+    uint32_t full_n = 0xDEADBEEFu; int error = 0;
+    for (uint32_t g = 0; g < G; ++g) gene_frag[g] = 0ull;
+
+    wavemu::set_seed(sched_seed);
+    struct Unseed { ~Unseed() { wavemu::set_seed(0); } } unseed;
+    wavemu::grid_dim().x = lay_blocks;
+    for (uint32_t b = 0; b < lay_blocks; ++b) { wavemu::block_idx().x = b; wavemu::run_block(1024, [&]() { frag_layout_totals_kernel(gene_reads.data(), G, blk_space.data(), blk_parts.data(), &error); }); }
+    for (uint32_t b = 0; b < lay_blocks; ++b) { wavemu::block_idx().x = b; wavemu::run_block(1024, [&]() { frag_layout_kernel(gene_reads.data(), G, blk_space.data(), blk_parts.data(), part_first.data(), ginfo.data(), cursor.data(), part_info.data(), &full_n); }); }
+    const uint32_t n_parts = part_first[G];
+    for (uint32_t g = 0; g <= G; ++g) part_first_out[g] = part_first[g];
+    memcpy(ginfo_out, ginfo.data(), (size_t)G * sizeof(uint4));
+    memcpy(part_info_out, part_info.data(), (size_t)parts_bound * sizeof(uint4));
+    *full_n_out = full_n; *error_out = error;
+    if (n_parts > parts_bound || full_n != 0u) return -1000;
+    {   // the key lists stay inside the allocation
+        unsigned long long end = 0;
+        for (uint32_t w = 0; w < n_parts; ++w) { const unsigned long long off = (unsigned long long)part_info[w].z | ((unsigned long long)part_info[w].w << 32); end = std::max(end, off + part_info[w].y); }
+        if (end > keys_bound) return -1000;
+    }
+
+    const uint32_t slow_base = n_chunks * chunk_cap;
+    std::vector<PairRec> pairs((size_t)slow_base + slow_cap + 1, PairRec{G, 0xDEADu, 0x5EEDull});
+    std::vector<uint32_t> cnt(counts, counts + n_chunks + 1);
+    {
+        uint64_t i = 0;
+        for (uint32_t c = 0; c <= n_chunks; ++c) {
+            const size_t base = c < n_chunks ? (size_t)c * chunk_cap : slow_base;
+            for (uint32_t k = 0; k < counts[c]; ++k, ++i) pairs[base + k] = PairRec{gene[i], h2[i], key[i]};
+        }
+    }
+    const uint32_t grid = frag_local_chunk_wgs(n_chunks) + sharers;
+    wavemu::grid_dim().x = grid;
+    for (uint32_t b = 0; b < grid; ++b) {
+        wavemu::block_idx().x = b;
+        wavemu::run_block(RSQC_K4L_THREADS, [&]() { frag_local_kernel(pairs.data(), chunk_cap, cnt.data(), n_chunks, slow_base, slow_cap, ginfo.data(), cursor.data(), list.data(), &error); });
+    }
+    memcpy(cursor_out, cursor.data(), (size_t)parts_bound * sizeof(uint32_t));
+    int rc = 0;
+    {   // nothing was stored beyond a partition's fill (clamped to its capacity)
+        std::vector<uint8_t> mine(keys_bound, 0);
+        for (uint32_t w = 0; w < n_parts; ++w) {
+            const unsigned long long off = (unsigned long long)part_info[w].z | ((unsigned long long)part_info[w].w << 32);
+            const uint32_t n = std::min(cursor[w], part_info[w].y);
+            for (uint32_t k = 0; k < n; ++k) mine[off + k] = 1;
+        }
+        for (uint64_t i = 0; i < keys_bound; ++i) if (!mine[i] && (list[i].lo != poison.lo || list[i].hi != poison.hi || list[i].h2 != poison.h2)) { rc = -1003; break; }
+    }
+
+    wavemu::grid_dim().x = grid_small;
+    for (uint32_t b = 0; b < grid_small; ++b) { wavemu::block_idx().x = b; wavemu::run_block(RSQC_K4_COUNT_THREADS, [&]() { frag_count_kernel<RSQC_K4_PART_SLOTS / 2>(part_first.data() + G, cursor.data(), part_info.data(), list.data(), gene_frag, full_list.data(), &full_n, &error); }); }
+    wavemu::grid_dim().x = grid_large;
+    for (uint32_t b = 0; b < grid_large; ++b) { wavemu::block_idx().x = b; wavemu::run_block(RSQC_K4_COUNT_THREADS, [&]() { frag_count_kernel<RSQC_K4_PART_SLOTS>(part_first.data() + G, cursor.data(), part_info.data(), list.data(), gene_frag, full_list.data(), &full_n, &error); }); }
+    memcpy(full_list_out, full_list.data(), (size_t)parts_bound * sizeof(uint32_t));
+    *full_n_out = full_n; *error_out = error;
+    return rc;
+}
