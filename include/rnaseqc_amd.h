@@ -631,6 +631,49 @@ typedef struct rsqc_sort_info {
 RSQC_API int rsqc_sort_begin(rsqc_ctx *ctx);
 RSQC_API int rsqc_sort_end(rsqc_ctx *ctx, rsqc_sort_info *out);
 
+/* ---- duplicate fragments flagged on the collection (additive to ABI 6) -----------------------------------------------------
+ * Behind rsqc_markdup_begin, rsqc_sort_end first runs one block of device work on the complete collection that REWRITES flag 0x400
+ * of every record; the per-read kernels then see those flags.  No per-read kernel, no other launch and no other output changes.
+ * The contract, in integers (tests/markdup_ref.py is its executable form; no equality with Picard or samtools is claimed):
+ *   population   a record is in it iff (flag & (0x4 | 0x100 | 0x200 | 0x800)) == 0 and its contig id (the tid of its segment, as the
+ *                collection's key column holds it) is >= 0 as a signed number.  Only population records can anchor a fragment.
+ *   u5           the unclipped 5' coordinate, in 32-bit two's-complement arithmetic (wrap-around is part of the contract).  Forward
+ *                strand (0x10 clear): pos - the lengths of the leading run of S / H operations.  Reverse strand: pos + the reference
+ *                length (M D N = X) + the lengths of the trailing run of S / H.  I and P contribute nothing, nor does an operation
+ *                code above 8 (the per-read kernels report that record later).  A record without CIGAR has u5 = pos; a record
+ *                stored with the n_cigar escape takes its length from the wide table; no read passes the collected operations.
+ *   kind, anchor SINGLE (0): not paired (0x1 clear) or mate unmapped (0x8) -- the record itself anchors.  PAIR (1): paired, mate
+ *                mapped, RSQC_TB_MTID_SAME -- the mate with pos < mpos, or pos == mpos and 0x40 set, anchors.  SPLIT (2): paired, mate
+ *                mapped, mate on another contig -- the record with 0x40 anchors.  A fragment without an anchor is never judged.
+ *   signature    of an anchor: (tid, u5, rev = 0x10, mrev = 0x20 (0 for SINGLE), kind, w) with w = isize for PAIR, mpos for SPLIT,
+ *                0 for SINGLE.
+ *   sets         anchors with equal signatures form a set; its survivor is the anchor with the highest mapq, ties keep the earliest
+ *                in arrival order; every other anchor of the set is a duplicate fragment.
+ *   verdicts     a record leaves with 0x400 set iff its name equals the name of a duplicate anchor -- every record of the
+ *                collection, whatever its flags or placement.  The name is (qhash, qhash2), or qhash alone in a pass without the
+ *                qhash2 column.  Every other record leaves with 0x400 clear: flags the input carried are replaced.
+ *   limits       the mate's own clipping is seen only through isize (the key UMI-tools uses, not Picard's); a SPLIT signature does
+ *                not know the mate's contig; no rule makes a SINGLE read a duplicate of a pair's end; base qualities are not in
+ *                the record, so mapq picks the survivor; an input whose names are not unique per fragment gets every record of a
+ *                flagged name flagged.
+ * rsqc_markdup_begin: behind rsqc_sort_begin and before the pass's first submit (RSQC_ERR_ARG otherwise); in any order relative to
+ * rsqc_junctions_begin and rsqc_track_begin.  rsqc_markdup_end: behind rsqc_sort_end (RSQC_ERR_ARG otherwise); a second call returns
+ * the same figures without device work.  rsqc_markdup_verdicts: one byte (0 or 1) per record of the collection in ARRIVAL order, rows
+ * [first, first + n); the host array is owned by the context and valid until its next call.  Memory during the stage: 44 bytes per
+ * anchor (two key columns and the sort's two key buffers, the record index and the sort's two payload buffers), half a byte per anchor
+ * for the digit histograms, 4 bytes per 256 records, 4 bytes per slot of the name table (a power of two >= twice the duplicate fragments, >= 1024) and one byte per record; all but the last is released before the
+ * coordinate sort allocates.  An allocation the device refuses is RSQC_ERR_CAPACITY with the sizes in rsqc_last_error and voids the
+ * pass as a failing rsqc_sort_end does: never a partly marked run.  rsqc_reset, rsqc_clear_inputs and rsqc_destroy end the mode.     */
+typedef struct rsqc_markdup_info {
+    uint64_t records, population, anchors, sets, duplicate_fragments;
+    uint64_t flagged_records;          /* records that leave with 0x400 set                                           */
+    uint64_t cleared_records;          /* records that arrived with 0x400 and leave without                           */
+    double   sig_ms, sort_ms, mark_ms; /* anchors and signatures; the two sort stages; heads, name set and apply (host clocks, as rsqc_sort_info's) */
+} rsqc_markdup_info;
+RSQC_API int rsqc_markdup_begin(rsqc_ctx *ctx);
+RSQC_API int rsqc_markdup_end(rsqc_ctx *ctx, rsqc_markdup_info *out);
+RSQC_API int rsqc_markdup_verdicts(rsqc_ctx *ctx, uint64_t first, uint64_t n, const uint8_t **dup);
+
 /* ---- reads per splice junction (additive to ABI 6) ---------------------------------------------------------------------
  * Between rsqc_junctions_begin and the end of the pass every batch that the per-read kernels run also leaves its splice-junction
  * INSTANCES on the device (one extra kernel per batch; no other kernel, output or launch changes), and rsqc_junctions_end orders

@@ -190,6 +190,11 @@ class SortInfo(C.Structure):
                 ("key_ms", C.c_double), ("sort_ms", C.c_double), ("gather_ms", C.c_double), ("was_sorted", C.c_int32)]
 
 
+class MarkdupInfo(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("population", C.c_uint64), ("anchors", C.c_uint64), ("sets", C.c_uint64), ("duplicate_fragments", C.c_uint64),
+                ("flagged_records", C.c_uint64), ("cleared_records", C.c_uint64), ("sig_ms", C.c_double), ("sort_ms", C.c_double), ("mark_ms", C.c_double)]
+
+
 class JunctionTable(C.Structure):
     _fields_ = [("n", C.c_uint64), ("instances", C.c_uint64), ("population", C.c_uint64),
                 ("tid", _P), ("start", _P), ("end", _P), ("reads", _P), ("hq_reads", _P), ("max_overhang", _P),

@@ -54,6 +54,7 @@ struct Options {
     std::string bam_list; bool has_bam_list = false;   // --bam-list (extension): a cohort, the positionals are `gtf output`
     bool bedgraph = false;             // --bedgraph (extension): the per-base coverage track, <sample>.coverage.bedgraph (rsqc_track_begin / _end / _text)
     bool junctions = false;            // --junctions (extension): reads per splice junction, <sample>.junctions.tsv (rsqc_junctions_begin / rsqc_junctions_end)
+    bool mark_duplicates = false;      // --mark-duplicates (extension, implies --sort): flag 0x400 rewritten on the GPU before the records are counted (rsqc_markdup_begin / rsqc_markdup_end)
     bool sort = false;                 // --sort (extension): input in any order, put in coordinate order on the GPU (rsqc_sort_begin / rsqc_sort_end)
 };
 
@@ -88,6 +89,7 @@ void usage(std::ostream &o) {
          "      --gpus=[N]                        (extension) Shard the BAM by contig over N GPUs of this node; needs [bam].bai. Default: 1\n"
          "      --bam-list=[FILE]                 (extension) A cohort on one GPU: FILE lists one input per line, path[<TAB>sample]; the positionals are [gtf] [output]\n"
          "      --sort                            (extension) Accept input in any order: the records are put in coordinate order on the GPU before they are counted\n"
+         "      --mark-duplicates                 (extension) Flag duplicate fragments on the GPU before they are counted: implies --sort, replaces the input's 0x400 flags (one GPU, one input)\n"
          "      --junctions                       (extension) Count reads per splice junction on the GPU and write [sample].junctions.tsv (one GPU)\n"
          "      --bedgraph                        (extension) Build the per-base coverage track on the GPU and write [sample].coverage.bedgraph (one GPU; needs LN in the header)\n";
 }
@@ -169,6 +171,7 @@ Options parse(int argc, char **argv) {
         else if (name == "gpus") o.gpus = (int)to_ulong(name, need());
         else if (name == "bam-list") { o.bam_list = need(); o.has_bam_list = true; }
         else if (name == "sort") o.sort = true;
+        else if (name == "mark-duplicates") o.mark_duplicates = o.sort = true;
         else if (name == "junctions") o.junctions = true;
         else if (name == "bedgraph") o.bedgraph = true;
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
@@ -782,6 +785,8 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     rc = RSQC_OK;
     // --sort: the loops below collect (no per-read kernel runs); rsqc_sort_end orders the records and runs them
     if (o.sort && (rc = rsqc_sort_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    // --mark-duplicates: rsqc_sort_end first rewrites flag 0x400 of the collection
+    if (o.mark_duplicates && (rc = rsqc_markdup_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --junctions: every batch the per-read kernels run leaves its junction instances on the device (under --sort: the sorted batches)
     if (o.junctions && (rc = rsqc_junctions_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --bedgraph: and its coverage events, in a difference array over the header's contigs (kept by the context while it is large enough)
@@ -877,6 +882,11 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
             cout << "Sorted on the GPU: records " << sort_info.records << ", batches in " << sort_info.batches_in << ", batches out " << sort_info.batches_out
                  << ", moved " << sort_info.moved << ", key_ms " << sort_info.key_ms << ", sort_ms " << sort_info.sort_ms << ", gather_ms " << sort_info.gather_ms
                  << ", was_sorted " << sort_info.was_sorted << endl;
+        rsqc_markdup_info md{};
+        if (o.mark_duplicates && (rc = rsqc_markdup_end(gpu, &md)) == RSQC_OK && o.verbosity)
+            cout << "Duplicates marked: records " << md.records << ", population " << md.population << ", anchors " << md.anchors << ", sets " << md.sets
+                 << ", duplicate_fragments " << md.duplicate_fragments << ", flagged_records " << md.flagged_records << ", cleared_records " << md.cleared_records
+                 << ", sig_ms " << md.sig_ms << ", sort_ms " << md.sort_ms << ", mark_ms " << md.mark_ms << endl;
     }
     rsqc_results res{};
     if (rc == RSQC_OK) rc = rsqc_finalize(gpu, &res);
@@ -1211,6 +1221,13 @@ int main(int argc, char **argv) {
             if (o.stranded == "RF" || o.stranded == "rf") strand = RSQC_STRAND_REVERSE;
             else if (o.stranded == "FR" || o.stranded == "fr") strand = RSQC_STRAND_FORWARD;
             else throw ValidationError("--stranded argument must be in {'RF', 'rf', 'FR', 'fr'}");
+        }
+        if (o.mark_duplicates) {
+            // the whole input must be resident: the stage runs on the collection of --sort, in ONE context
+            if (o.has_bam_list) throw ValidationError("--mark-duplicates takes one input (it cannot be combined with --bam-list)");
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--mark-duplicates runs on one GPU (it implies --sort: it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
         }
         if (o.sort) {
             // the sort sits in front of ONE context's ordinary submits: contig sharding needs the index of a sorted file, cohorts are not collected

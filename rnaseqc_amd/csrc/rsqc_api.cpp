@@ -117,6 +117,7 @@ void rsqc_destroy(rsqc_ctx *c) {
         for (auto &e : D.pe) if (e) (void)hipEventDestroy(e);
     }
     sort_drop(c);
+    markdup_drop(c);
     junction_drop(c, true);
     track_drop(c, true);
     for (auto &b : c->parked) b.release();
@@ -355,6 +356,7 @@ int rsqc_reset(rsqc_ctx *c) {
     HIP_TRY(c, hipSetDevice(c->device));
     RSQC_TRACE("reset: enter");
     if (c->sort.active || c->sort.core.p) sort_drop(c);
+    markdup_drop(c);
     junction_drop(c, false);                           // (the columns stay for the next pass)
     track_drop(c, false);                              // (and so does the difference array)
     const int rc = zero_accumulators(c);
@@ -374,6 +376,7 @@ int rsqc_clear_inputs(rsqc_ctx *c) {
     c->transient.clear();
     free_parked(c);
     sort_drop(c);
+    markdup_drop(c);
     junction_drop(c, false);
     track_drop(c, false);
     // an open decode stream is dropped with its carried-over bytes; its window buffers stay

@@ -148,6 +148,17 @@ struct JunctionState {
     rsqc_junction_table table{};
 };
 
+// --mark-duplicates (rsqc_markdup_begin / rsqc_markdup_end / rsqc_markdup_verdicts, rsqc_markdup_api.cpp): the figures of the stage that
+// rsqc_sort_end ran, the verdict column (one byte per record of the collection, in arrival order), one window of it on the host
+struct MarkdupState {
+    bool active = false, done = false;
+    uint64_t n = 0;                                    // records of the collection the verdicts are for
+    int passes_lo = 0, passes_hi = 0;                  // live radix passes of the two sort stages
+    rsqc_markdup_info info{};
+    DevBuf verdict;
+    std::vector<uint8_t> h_verdict;                    // the window of the last rsqc_markdup_verdicts
+};
+
 // --bedgraph (rsqc_track_begin / rsqc_track_end / rsqc_track_rows / rsqc_track_text, rsqc_track_api.cpp): the difference array of
 // the pass (4 bytes per reference position, kept across rsqc_reset), the rows on the device (16 bytes each), one window on the host
 struct TrackState {
@@ -256,6 +267,7 @@ struct rsqc_ctx {
     SortState sort;
     JunctionState junc;
     TrackState track;
+    MarkdupState markdup;
 
     // host results
     std::vector<uint64_t> h_fcount;
@@ -290,6 +302,9 @@ const char *device_error_text(int err);
 // collecting mode: the batch's records are appended to the collection instead of being run (rsqc_sort_api.cpp)
 int sort_append(rsqc_ctx *c, UploadedBatch *u);
 void sort_drop(rsqc_ctx *c);                   // leaves the collecting mode and frees the collection (hipFree waits for the device)
+// --mark-duplicates: the stage at the head of rsqc_sort_end, on the complete collection (rsqc_markdup_api.cpp)
+int markdup_run(rsqc_ctx *c);
+void markdup_drop(rsqc_ctx *c);                // ends the mode and frees the verdict column
 // --junctions: the batch's instances appended to the collection, on the main stream (rsqc_junction_api.cpp)
 int junction_extract(rsqc_ctx *c, const UploadedBatch *u, const DevBatch &d);
 void junction_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the instances

@@ -1,0 +1,244 @@
+// rsqc_markdup.h -- the kernels of --mark-duplicates (rsqc_markdup_begin / rsqc_markdup_end / rsqc_markdup_verdicts): one block of
+// work at the head of rsqc_sort_end, on the complete collection, that rewrites flag bit 0x400 of every record.  The contract is
+// written out in include/rnaseqc_amd.h and restated in tests/markdup_ref.py.  Written like rsqc_sort.h against the HIP wave
+// intrinsics only (__ballot, __shfl*, LDS, global atomics): the same source runs under the 64-lane emulation of
+// tests/hostemu/wavemu.h (tests/hostemu/markdup_emu.cpp).  No rocPRIM.  One lane per item everywhere:
+//
+//   markdup_mark_kernel        per record the anchor predicate; a workgroup leaves the NUMBER of its anchors (and adds its population
+//                              records to a counter with one atomic).  launch_sort_scan over those per-workgroup numbers gives every
+//                              workgroup its first slot -- 4 bytes per 256 records instead of 4 per record
+//   markdup_signature_kernel   the predicate again, a workgroup scan for the slot inside the workgroup (lanes are records in arrival
+//                              order, so slots keep that order: the tie rule needs it), and per anchor K_hi, K_lo and its collection index
+//   (the order: rsqc_sort.h's radix pass, launch_sort_pass, LSD in two stages -- by K_lo with the slot as payload, then stably by K_hi
+//    gathered through the payload with markdup_permute_kernel; dead digit positions are skipped in both)
+//   markdup_heads_kernel       1 where a sorted anchor has the signature of its predecessor: a duplicate anchor
+//   markdup_list_kernel        after the prefix sum of those marks: D, the collection indices of the duplicate anchors
+//   markdup_insert_kernel      the names of D into an open-addressing table of uint32 slots (index in D), linear probing from
+//                              qhash & mask; names are compared through D's records, which are complete before the kernel: WHICH index
+//                              of an equal name wins a slot depends on the schedule, whether a name is in the table does not
+//   markdup_apply_kernel       per record: probe until an equal name or an empty slot, rewrite the flag of its OWN record (a 16-bit
+//                              store: other lanes read the qhash beside it), the verdict byte, and two counters -- a ballot and a
+//                              popcount per wave, then one atomic per wave and counter
+#pragma once
+
+#if !defined(RSQC_WAVE_EMU)
+#include <hip/hip_runtime.h>
+#endif
+#include <stdint.h>
+
+#include "../../include/rnaseqc_amd.h"
+
+#define RSQC_MD_THREADS 256
+#define RSQC_MD_EMPTY 0xFFFFFFFFu
+#define RSQC_MD_MIN_TABLE 1024u
+#define RSQC_MD_EXCLUDED (RSQC_FUNMAP | RSQC_FSECONDARY | RSQC_FQCFAIL | RSQC_FSUPP)
+#define RSQC_MD_SINGLE 0u
+#define RSQC_MD_PAIR 1u
+#define RSQC_MD_SPLIT 2u
+
+namespace rsqc {
+
+// the collection of rsqc_sort_begin as this stage reads it (device pointers).  `aux` is written: the flag of every record
+struct MarkdupCollection {
+    const rsqc_rec_core *core; rsqc_rec_aux *aux; const uint32_t *qhash2 /* or null: the name is qhash alone */; const uint64_t *key; const uint32_t *cigar;
+    uint64_t n;                                                        // records
+    const uint64_t *batch_rec0, *batch_pool0; uint32_t n_batches;      // first record / first operation of input batch k
+    const uint64_t *wide_index; const uint32_t *wide_n_cigar; uint64_t n_wide;
+    uint64_t n_ops;                                                    // operations in `cigar`: no record reads past them
+};
+
+// the size of the name table for n_dup duplicate anchors: a power of two, at least twice their number and at least 1024
+inline uint64_t markdup_table_size(uint64_t n_dup) {
+    uint64_t s = RSQC_MD_MIN_TABLE;
+    while (s < 2 * n_dup) s <<= 1;
+    return s;
+}
+
+#if defined(RSQC_MARKDUP_KERNELS) || defined(RSQC_WAVE_EMU)      /* the kernels: rsqc_markdup.hip and the emulation only */
+// exclusive prefix sum over the 256 lanes of a workgroup (every lane calls); total = the sum over all of them
+__device__ inline uint32_t md_block_scan(uint32_t v, uint32_t &total) {
+    __shared__ uint32_t s_wave[RSQC_MD_THREADS / 64];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t x = v;
+    for (uint32_t o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(x, o, 64); if (lane >= o) x += t; }
+    if (lane == 63) s_wave[w] = x;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+    for (uint32_t k = 0; k < RSQC_MD_THREADS / 64; ++k) { const uint32_t s = s_wave[k]; if (k < w) base += s; tot += s; }
+    __syncthreads();                                   // (the next call writes s_wave again)
+    total = tot;
+    return base + x - v;
+}
+
+// population and anchor of record i (i < C.n): kind is set for an anchor
+__device__ inline bool md_is_anchor(const MarkdupCollection &C, uint64_t i, const rsqc_rec_aux &a, bool &member, uint32_t &kind) {
+    const int32_t tid = (int32_t)(uint32_t)(C.key[i] >> 32);
+    member = (a.flag & RSQC_MD_EXCLUDED) == 0 && tid >= 0;
+    kind = RSQC_MD_SINGLE;
+    if (!member) return false;
+    if (!(a.flag & RSQC_FPAIRED) || (a.flag & RSQC_FMUNMAP)) return true;
+    if (a.tagbits & RSQC_TB_MTID_SAME) {
+        kind = RSQC_MD_PAIR;
+        const rsqc_rec_core c = C.core[i];
+        return c.pos < c.mpos || (c.pos == c.mpos && (a.flag & RSQC_FREAD1));
+    }
+    kind = RSQC_MD_SPLIT;
+    return (a.flag & RSQC_FREAD1) != 0;
+}
+
+// the unclipped 5' coordinate of record i, in 32-bit two's-complement arithmetic
+__device__ inline uint32_t md_u5(const MarkdupCollection &C, uint64_t i, const rsqc_rec_core &c, const rsqc_rec_aux &a) {
+    uint32_t n_ops = a.n_cigar;
+    if (a.n_cigar == RSQC_NCIGAR_ESCAPE) {             // the true count is in the wide table (an escape value without an entry: no operations)
+        uint64_t lo = 0, hi = C.n_wide;
+        while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (C.wide_index[m] < i) lo = m + 1; else hi = m; }
+        n_ops = (lo < C.n_wide && C.wide_index[lo] == i) ? C.wide_n_cigar[lo] : 0u;
+    }
+    // the input batch of the record: the last one that starts at or before it (cigar_off is relative to ITS pool)
+    uint32_t lo = 0, hi = C.n_batches;
+    while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (C.batch_rec0[m] <= i) lo = m; else hi = m; }
+    const uint64_t src = C.batch_pool0[lo] + c.cigar_off;
+    if (src >= C.n_ops) n_ops = 0u; else if ((uint64_t)n_ops > C.n_ops - src) n_ops = (uint32_t)(C.n_ops - src);
+    const uint32_t *ops = C.cigar + src;
+    uint32_t u = (uint32_t)c.pos;
+    if (!(a.flag & RSQC_FREVERSE)) {
+        for (uint32_t k = 0; k < n_ops; ++k) {
+            const uint32_t op = ops[k], code = op & 15u;
+            if (code != 4u && code != 5u) break;
+            u -= op >> 4;
+        }
+        return u;
+    }
+    uint32_t trail = 0; bool in_tail = true;           // from the last operation down: the trailing run of S / H ends at the first other code
+    for (uint32_t k = n_ops; k > 0; --k) {
+        const uint32_t op = ops[k - 1], code = op & 15u, len = op >> 4;
+        if (in_tail && (code == 4u || code == 5u)) { trail += len; continue; }
+        in_tail = false;
+        if (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) u += len;
+    }
+    return u + trail;
+}
+
+__device__ inline bool md_same_name(const MarkdupCollection &C, uint64_t i, uint64_t qhash, uint32_t qh2) {
+    return C.aux[i].qhash == qhash && (!C.qhash2 || C.qhash2[i] == qh2);
+}
+
+// ---- stage 1: the anchors of every workgroup -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_mark_kernel(MarkdupCollection C, uint32_t *block_anchors, unsigned long long *counters /* [0] population */) {
+    const uint64_t i = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    bool member = false, anchor = false; uint32_t kind;
+    if (i < C.n) anchor = md_is_anchor(C, i, C.aux[i], member, kind);
+    uint32_t anchors = 0, members = 0;
+    (void)md_block_scan(anchor ? 1u : 0u, anchors);
+    (void)md_block_scan(member ? 1u : 0u, members);
+    if (threadIdx.x == 0) {
+        block_anchors[blockIdx.x] = anchors;
+        if (members) atomicAdd(&counters[0], (unsigned long long)members);
+    }
+}
+
+// ---- stage 2: block_slot = the exclusive prefix sum of block_anchors; n_anchors = their sum ------------------------------------
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_signature_kernel(MarkdupCollection C, const uint32_t *block_slot, uint64_t n_anchors,
+                                                                             uint64_t *k_hi, uint64_t *k_lo, uint64_t *k_lo_sort /* a second copy: the sort's first buffer */, uint32_t *ci) {
+    const uint64_t i = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    bool member = false, anchor = false; uint32_t kind = 0;
+    rsqc_rec_aux a{};
+    if (i < C.n) { a = C.aux[i]; anchor = md_is_anchor(C, i, a, member, kind); }
+    uint32_t total = 0;
+    const uint32_t at = md_block_scan(anchor ? 1u : 0u, total);
+    if (!anchor) return;
+    const uint64_t slot = (uint64_t)block_slot[blockIdx.x] + at;
+    if (slot >= n_anchors) return;                     // (never: a store is not let out of the columns)
+    const rsqc_rec_core c = C.core[i];
+    const uint32_t u5 = md_u5(C, i, c, a);
+    const uint32_t w = kind == RSQC_MD_PAIR ? (uint32_t)c.isize : kind == RSQC_MD_SPLIT ? (uint32_t)c.mpos : 0u;
+    const uint32_t rev = (a.flag & RSQC_FREVERSE) ? 1u : 0u, mrev = (kind != RSQC_MD_SINGLE && (a.flag & RSQC_FMREVERSE)) ? 1u : 0u;
+    const uint64_t hi = (C.key[i] & 0xFFFFFFFF00000000ull) | (uint64_t)(u5 ^ 0x80000000u);
+    const uint64_t lo = ((uint64_t)w << 32) | (uint64_t)(kind << 10) | (uint64_t)(rev << 9) | (uint64_t)(mrev << 8) | (uint64_t)(255u - (uint32_t)a.mapq);
+    k_hi[slot] = hi; k_lo[slot] = lo; k_lo_sort[slot] = lo; ci[slot] = (uint32_t)i;
+}
+
+// ---- stage 3 (between the two sort stages): K_hi in the order of the first stage ------------------------------------------------
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_permute_kernel(const uint64_t *k_hi, const uint32_t *idx, uint64_t n, uint64_t *key) {
+    const uint64_t r = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    if (r < n) { const uint32_t s = idx[r]; key[r] = s < n ? k_hi[s] : 0ull; }
+}
+
+// ---- stage 4: key = K_hi in sorted order, idx[r] = the slot of rank r, k_lo by slot ---------------------------------------------
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_heads_kernel(const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, uint64_t n, uint32_t *mark) {
+    const uint64_t r = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    if (r >= n) return;
+    uint32_t dup = 0u;
+    if (r > 0 && key[r] == key[r - 1]) {
+        const uint32_t s = idx[r], p = idx[r - 1];
+        if (s < n && p < n && (k_lo[s] >> 8) == (k_lo[p] >> 8)) dup = 1u;
+    }
+    mark[r] = dup;
+}
+// at: the exclusive prefix sum of the marks, total[0] their sum: rank r is a duplicate when the sum moves on behind it
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_list_kernel(const uint32_t *at, const unsigned long long *total, const uint32_t *idx, const uint32_t *ci, uint64_t n, uint32_t *dup_list) {
+    const uint64_t r = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    if (r >= n) return;
+    const uint32_t before = at[r], through = r + 1 < n ? at[r + 1] : (uint32_t)total[0];
+    const uint32_t s = idx[r];
+    if (through != before && (uint64_t)before < total[0] && s < n) dup_list[before] = ci[s];
+}
+
+// ---- stage 5: the names of the duplicate anchors; table: mask + 1 slots, all RSQC_MD_EMPTY --------------------------------------
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_insert_kernel(MarkdupCollection C, const uint32_t *dup_list, uint64_t n_dup, uint32_t *table, uint32_t mask) {
+    const uint64_t j = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    if (j >= n_dup) return;
+    const uint64_t i = dup_list[j];
+    if (i >= C.n) return;
+    const uint64_t qhash = C.aux[i].qhash; const uint32_t qh2 = C.qhash2 ? C.qhash2[i] : 0u;
+    uint32_t h = (uint32_t)qhash & mask;
+    for (uint32_t step = 0; step <= mask; ++step) {    // (the table is at most half full: an empty slot comes long before the probe wraps)
+        const uint32_t old = atomicCAS(&table[h], RSQC_MD_EMPTY, (uint32_t)j);
+        if (old == RSQC_MD_EMPTY) return;              // inserted
+        if ((uint64_t)old < n_dup) { const uint64_t o = dup_list[old]; if (o < C.n && md_same_name(C, o, qhash, qh2)) return; }   // the name is there
+        h = (h + 1u) & mask;
+    }
+}
+
+// ---- stage 6: table == nullptr: no duplicate anchor, every record leaves with 0x400 clear ---------------------------------------
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_apply_kernel(MarkdupCollection C, const uint32_t *dup_list, uint64_t n_dup, const uint32_t *table, uint32_t mask,
+                                                                         uint8_t *verdict, unsigned long long *counters /* [1] flagged, [2] cleared */) {
+    const uint64_t i = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    bool dup = false, cleared = false;
+    if (i < C.n) {
+        const rsqc_rec_aux a = C.aux[i];
+        if (table) {
+            const uint32_t qh2 = C.qhash2 ? C.qhash2[i] : 0u;
+            uint32_t h = (uint32_t)a.qhash & mask;
+            for (uint32_t step = 0; step <= mask; ++step) {
+                const uint32_t s = table[h];
+                if (s == RSQC_MD_EMPTY) break;
+                if ((uint64_t)s < n_dup) { const uint64_t o = dup_list[s]; if (o < C.n && md_same_name(C, o, a.qhash, qh2)) { dup = true; break; } }
+                h = (h + 1u) & mask;
+            }
+        }
+        cleared = (a.flag & RSQC_FDUP) && !dup;
+        const uint16_t flag = (uint16_t)((a.flag & ~RSQC_FDUP) | (dup ? RSQC_FDUP : 0));
+        if (flag != a.flag) C.aux[i].flag = flag;
+        verdict[i] = dup ? 1u : 0u;
+    }
+    const unsigned long long dmask = __ballot(dup), cmask = __ballot(cleared);
+    if ((threadIdx.x & 63u) == 0u) {
+        if (dmask) atomicAdd(&counters[1], (unsigned long long)__popcll(dmask));
+        if (cmask) atomicAdd(&counters[2], (unsigned long long)__popcll(cmask));
+    }
+}
+#endif
+
+#if !defined(RSQC_WAVE_EMU)
+// launchers (rsqc_markdup.hip)
+void launch_markdup_mark(hipStream_t s, const MarkdupCollection &C, uint32_t *block_anchors, unsigned long long *counters);
+void launch_markdup_signature(hipStream_t s, const MarkdupCollection &C, const uint32_t *block_slot, uint64_t n_anchors, uint64_t *k_hi, uint64_t *k_lo, uint64_t *k_lo_sort, uint32_t *ci);
+void launch_markdup_permute(hipStream_t s, const uint64_t *k_hi, const uint32_t *idx, uint64_t n, uint64_t *key);
+void launch_markdup_heads(hipStream_t s, const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, uint64_t n, uint32_t *mark);
+void launch_markdup_list(hipStream_t s, const uint32_t *at, const unsigned long long *total, const uint32_t *idx, const uint32_t *ci, uint64_t n, uint32_t *dup_list);
+void launch_markdup_insert(hipStream_t s, const MarkdupCollection &C, const uint32_t *dup_list, uint64_t n_dup, uint32_t *table, uint32_t mask);
+void launch_markdup_apply(hipStream_t s, const MarkdupCollection &C, const uint32_t *dup_list, uint64_t n_dup, const uint32_t *table, uint32_t mask, uint8_t *verdict, unsigned long long *counters);
+#endif
+
+}  // namespace rsqc

@@ -1,0 +1,44 @@
+// rsqc_markdup.hip -- launchers of the --mark-duplicates kernels (rsqc_markdup.h); the host side that drives them is rsqc_markdup_api.cpp.
+#define RSQC_MARKDUP_KERNELS
+#include "rsqc_markdup.h"
+
+namespace rsqc {
+
+static inline uint32_t blocks_for(uint64_t n, uint32_t per_block) { return (uint32_t)((n + per_block - 1) / per_block); }
+
+void launch_markdup_mark(hipStream_t s, const MarkdupCollection &C, uint32_t *block_anchors, unsigned long long *counters) {
+    if (!C.n) return;
+    markdup_mark_kernel<<<blocks_for(C.n, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(C, block_anchors, counters);
+}
+
+void launch_markdup_signature(hipStream_t s, const MarkdupCollection &C, const uint32_t *block_slot, uint64_t n_anchors, uint64_t *k_hi, uint64_t *k_lo, uint64_t *k_lo_sort, uint32_t *ci) {
+    if (!C.n || !n_anchors) return;
+    markdup_signature_kernel<<<blocks_for(C.n, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(C, block_slot, n_anchors, k_hi, k_lo, k_lo_sort, ci);
+}
+
+void launch_markdup_permute(hipStream_t s, const uint64_t *k_hi, const uint32_t *idx, uint64_t n, uint64_t *key) {
+    if (!n) return;
+    markdup_permute_kernel<<<blocks_for(n, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(k_hi, idx, n, key);
+}
+
+void launch_markdup_heads(hipStream_t s, const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, uint64_t n, uint32_t *mark) {
+    if (!n) return;
+    markdup_heads_kernel<<<blocks_for(n, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(key, idx, k_lo, n, mark);
+}
+
+void launch_markdup_list(hipStream_t s, const uint32_t *at, const unsigned long long *total, const uint32_t *idx, const uint32_t *ci, uint64_t n, uint32_t *dup_list) {
+    if (!n) return;
+    markdup_list_kernel<<<blocks_for(n, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(at, total, idx, ci, n, dup_list);
+}
+
+void launch_markdup_insert(hipStream_t s, const MarkdupCollection &C, const uint32_t *dup_list, uint64_t n_dup, uint32_t *table, uint32_t mask) {
+    if (!n_dup) return;
+    markdup_insert_kernel<<<blocks_for(n_dup, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(C, dup_list, n_dup, table, mask);
+}
+
+void launch_markdup_apply(hipStream_t s, const MarkdupCollection &C, const uint32_t *dup_list, uint64_t n_dup, const uint32_t *table, uint32_t mask, uint8_t *verdict, unsigned long long *counters) {
+    if (!C.n) return;
+    markdup_apply_kernel<<<blocks_for(C.n, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(C, dup_list, n_dup, table, mask, verdict, counters);
+}
+
+}  // namespace rsqc

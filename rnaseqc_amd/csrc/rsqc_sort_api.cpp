@@ -77,8 +77,9 @@ int sort_end_run(rsqc_ctx *c, EndScratch &X, rsqc_sort_info &info) {
     info.records = N; info.batches_in = S.batches_in;
     HIP_TRY(c, hipStreamSynchronize(c->stream));                       // (the collection is complete; parked columns can go)
     free_parked(c);
-    if (N == 0) { info.was_sorted = 1; return 0; }
     int rc;
+    if (c->markdup.active && (rc = markdup_run(c))) return rc;          // --mark-duplicates: flag 0x400 of the collection is rewritten first
+    if (N == 0) { info.was_sorted = 1; return 0; }
     // ---- the payload, and what the keys say about the work: OR, AND, order
     // (key_ms and sort_ms are host clocks around kernels and the synchronisation behind them: every allocation is made before its clock starts)
     const uint32_t prep_grid = (uint32_t)std::min<uint64_t>(RSQC_SORT_PREP_GRID, (N + RSQC_SORT_THREADS - 1) / RSQC_SORT_THREADS);
@@ -253,6 +254,7 @@ int rsqc_sort_begin(rsqc_ctx *c) {
         return fail(c, RSQC_ERR_ARG, "rsqc_sort_begin must precede the first submit of the pass");
     HIP_TRY(c, hipSetDevice(c->device));
     sort_drop(c);
+    markdup_drop(c);
     c->sort.active = true;
     return RSQC_OK;
 }

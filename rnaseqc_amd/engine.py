@@ -73,6 +73,9 @@ def load_library():
         lib.rsqc_decode_submit_text.argtypes = [vp, vp, C.c_uint64, C.POINTER(abi.DecodeWindow)]
         lib.rsqc_sort_begin.argtypes = [vp]
         lib.rsqc_sort_end.argtypes = [vp, C.POINTER(abi.SortInfo)]
+        lib.rsqc_markdup_begin.argtypes = [vp]
+        lib.rsqc_markdup_end.argtypes = [vp, C.POINTER(abi.MarkdupInfo)]
+        lib.rsqc_markdup_verdicts.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]
         lib.rsqc_junctions_begin.argtypes = [vp]
         lib.rsqc_junctions_end.argtypes = [vp, C.POINTER(abi.JunctionTable)]
         lib.rsqc_track_begin.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_char_p)]
@@ -90,7 +93,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_group_create", "rsqc_group_reduce", "rsqc_group_info", "rsqc_group_destroy", "rsqc_refresh_results", "rsqc_finalize_device", "rsqc_host_alloc", "rsqc_host_free", "rsqc_strerror",
     "rsqc_last_error", "rsqc_counter_name", "rsqc_version", "rsqc_qname_hash", "rsqc_qname_hash2",
     "rsqc_decode_begin", "rsqc_decode_submit", "rsqc_decode_end", "rsqc_decode_begin_sam", "rsqc_decode_submit_text",
-    "rsqc_sort_begin", "rsqc_sort_end", "rsqc_junctions_begin", "rsqc_junctions_end",
+    "rsqc_sort_begin", "rsqc_sort_end", "rsqc_markdup_begin", "rsqc_markdup_end", "rsqc_markdup_verdicts", "rsqc_junctions_begin", "rsqc_junctions_end",
     "rsqc_track_begin", "rsqc_track_end", "rsqc_track_rows", "rsqc_track_text",
 ]
 
@@ -246,6 +249,23 @@ class Engine:
         info = abi.SortInfo()
         self._check(self._l.rsqc_sort_end(self._h, C.byref(info)))
         return {f: getattr(info, f) for f, _ in abi.SortInfo._fields_}
+
+    # ---- duplicate fragments flagged on the collection (rsqc_markdup_*) ------------------------------------------
+    def markdup_begin(self):
+        """Behind sort_begin(), before the first submit: sort_end() first rewrites flag 0x400 of every collected record."""
+        self._check(self._l.rsqc_markdup_begin(self._h))
+
+    def markdup_end(self) -> dict:
+        """Behind sort_end(): the fields of rsqc_markdup_info."""
+        info = abi.MarkdupInfo()
+        self._check(self._l.rsqc_markdup_end(self._h, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in abi.MarkdupInfo._fields_}
+
+    def markdup_verdicts(self, first, n) -> np.ndarray:
+        """One byte (0 or 1) per record of the collection in arrival order, rows [first, first + n) (a copy)."""
+        p = C.c_void_p()
+        self._check(self._l.rsqc_markdup_verdicts(self._h, int(first), int(n), C.byref(p)))
+        return abi._view(p.value, int(n), np.uint8)
 
     # ---- reads per splice junction (rsqc_junctions_*) -------------------------------------------------------------
     def junctions_begin(self):
