@@ -9,7 +9,7 @@
 // library radix sorts and replayed a whole group on one thread of a grid over ALL candidates):
 //
 //   K1 emits one candidate per record that passes the per-record tests (HQ, paired, every block inside one BED interval);
-//   pair_bucket_*   the candidates are PARTITIONED by the high word of their name hash into buckets of ~512 (count, scan,
+//   pair_bucket_*   the candidates are PARTITIONED by the high word of their name hash into buckets of 384 on average (PB_MEAN; count, scan,
 //                   scatter of candidate indices: three streaming passes with one memory atomic per candidate each);
 //   *_replay_kernel one workgroup per bucket: the bucket's (name hash, file index, candidate) triples are loaded into LDS and
 //                   sorted there (bitonic network, 2048 slots), so that a name's records are adjacent and in file order; the
@@ -30,6 +30,7 @@
 
 #include "rsqc_device.h"
 
+#include "rsqc_k5_plan.h"
 #include "rsqc_k5.h"
 
 namespace rsqc {
@@ -58,10 +59,10 @@ int grow_scratch(SortScratch &S, uint32_t n) {
 struct Buckets { uint32_t n_buckets; uint32_t *count, *off, *cursor, *big; };
 // partitions `n` candidates by name hash: S.v2 = candidate indices bucket by bucket, offsets in the returned arrays
 int partition_by_name(hipStream_t stream, const uint64_t *qhash, uint32_t n, SortScratch &S, int *d_error, Buckets &B) {
-    B.n_buckets = std::max<uint32_t>(1u, n / PB_MEAN);
+    B.n_buckets = k5_bucket_count(n);
     B.count = (uint32_t *)S.tmp; B.off = B.count + (B.n_buckets + 1); B.cursor = B.off + (B.n_buckets + 1); B.big = B.cursor + (B.n_buckets + 1);
     if (hipMemsetAsync(B.count, 0, (size_t)(B.n_buckets + 1) * 4, stream) != hipSuccess || hipMemsetAsync(B.big, 0, 4, stream) != hipSuccess) return RSQC_ERR_HIP;
-    const int T = 256, G = (int)((n + T - 1) / T);
+    const int T = (int)K5_PART_THREADS, G = (int)k5_part_grid(n);
     hipLaunchKernelGGL(pair_bucket_count_kernel, dim3(G), dim3(T), 0, stream, qhash, n, B.n_buckets, B.count);
     hipLaunchKernelGGL(pair_bucket_scan_kernel, dim3(1), dim3(1024), 0, stream, B.count, B.n_buckets, B.off, B.cursor, B.big, d_error);
     hipLaunchKernelGGL(pair_bucket_scatter_kernel, dim3(G), dim3(T), 0, stream, qhash, n, B.n_buckets, B.cursor, (uint32_t *)S.v2);
@@ -92,24 +93,24 @@ int run_fragment_sizes(hipStream_t stream, const FragCandidates &c, uint32_t n, 
     if (partition_by_name(stream, c.qhash, n, S, d_error, B)) return RSQC_ERR_HIP;
     hipLaunchKernelGGL(frag_replay_kernel, dim3(B.n_buckets), dim3(PB_THREADS), 0, stream, c, B.off, (const uint32_t *)S.v2, s_file, s_size, ctl + 0);
     // (the buckets the LDS sort cannot hold -- none with ordinary read names: the kernel then finds an empty list)
-    hipLaunchKernelGGL(frag_replay_big_kernel, dim3(64), dim3(1024), 0, stream, c, B.off, (const uint32_t *)S.v2, B.big, (uint32_t *)S.v3, s_file, s_size, ctl + 0);
+    hipLaunchKernelGGL(frag_replay_big_kernel, dim3(K5_BIG_GRID), dim3(1024), 0, stream, c, B.off, (const uint32_t *)S.v2, B.big, (uint32_t *)S.v3, s_file, s_size, ctl + 0);
     // (3) the first max_samples samples in file order: a radix select of the sample of rank min(samples, max_samples) among the file
     //     indices, decided ON THE DEVICE digit by digit (round 4 read 256 counters back per digit and the sample count before: nine
     //     synchronous copies per pass); with fewer samples than the limit it selects the last one and everything is kept
     if (max_samples == 0) return 0;
     uint64_t *state = (uint64_t *)(ctl + 264);
     hipLaunchKernelGGL(sample_plan_kernel, dim3(1), dim3(64), 0, stream, ctl + 0, max_samples, state);
-    const uint32_t ns_bound = n / 2u + 1u;                              // (a sample takes two candidates)
-    const uint32_t sel_grid = std::min<uint32_t>(1024u, (ns_bound + 255u) / 256u);
+    const K5Plan plan = k5_plan(n, max_samples);                        // (ns_bound: a sample takes two candidates)
+    const uint32_t sel_grid = plan.select_grid;
     for (int shift = 56; shift >= 0; shift -= 8) {
         hipLaunchKernelGGL(sample_digit_hist_kernel, dim3(sel_grid), dim3(256), 0, stream, s_file, ctl + 0, shift, state, ctl + 8);
         hipLaunchKernelGGL(sample_digit_pick_kernel, dim3(1), dim3(256), 0, stream, ctl + 8, shift, state);
     }
-    hipLaunchKernelGGL(sample_keep_kernel, dim3((ns_bound + 1023) / 1024), dim3(1024), 0, stream, s_file, s_size, ctl + 0, state, k_file, k_size, ctl + 1);
+    hipLaunchKernelGGL(sample_keep_kernel, dim3(plan.keep_grid), dim3(1024), 0, stream, s_file, s_size, ctl + 0, state, k_file, k_size, ctl + 1);
     // (4) the histogram of the kept sizes as (size, count) pairs, ascending
     FS_TRY(hipMemsetAsync(S.table, 0, (size_t)SIZE_TABLE * 4, stream));
     uint32_t *big = (uint32_t *)S.v2;                                  // (the bucket order is no longer needed)
-    hipLaunchKernelGGL(size_hist_kernel, dim3(std::min<uint32_t>(512u, (std::min(ns_bound, max_samples) + 255u) / 256u)), dim3(256), 0, stream, k_size, ctl + 1, S.table, big, ctl + 3, ctl + 4);
+    hipLaunchKernelGGL(size_hist_kernel, dim3(plan.size_grid), dim3(256), 0, stream, k_size, ctl + 1, S.table, big, ctl + 3, ctl + 4);
     hipLaunchKernelGGL(size_hist_compact_kernel, dim3(1), dim3(1024), 0, stream, S.table, ctl + 4, S.out_size, S.out_count, ctl + 2);
     // ONE read-back: the control words and the first pairs (a fragment-size histogram has a few hundred distinct sizes)
     uint32_t tail[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -151,7 +152,7 @@ int run_gc_content(hipStream_t stream, const GcCandidates &c, uint32_t n, const 
     Buckets B;
     if (partition_by_name(stream, c.qhash, n, S, d_error, B)) return RSQC_ERR_HIP;
     hipLaunchKernelGGL(gc_replay_kernel, dim3(B.n_buckets), dim3(PB_THREADS), 0, stream, c, B.off, (const uint32_t *)S.v2, R, bins);
-    hipLaunchKernelGGL(gc_replay_big_kernel, dim3(64), dim3(1024), 0, stream, c, B.off, (const uint32_t *)S.v2, B.big, (uint32_t *)S.v3, R, bins);
+    hipLaunchKernelGGL(gc_replay_big_kernel, dim3(K5_BIG_GRID), dim3(1024), 0, stream, c, B.off, (const uint32_t *)S.v2, B.big, (uint32_t *)S.v3, R, bins);
     return hipGetLastError() == hipSuccess ? 0 : RSQC_ERR_HIP;
 }
 

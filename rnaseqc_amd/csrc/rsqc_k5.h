@@ -3,9 +3,10 @@
 // the host side) and, unmodified, by the host SIMT emulation of the tests (tests/hostemu/k5_emu.cpp; the GC replay: tests/hostemu/gc_emu.cpp).
 #pragma once
 
+#include "rsqc_k5_plan.h"                    // PB_MEAN (candidates per bucket on average) and the host's launch plan
+
 namespace rsqc {
 
-constexpr uint32_t PB_MEAN = 384;            // candidates per bucket on average (the name hashes are fmix64 outputs: Poisson; <= 512, the hashed pairing's limit, in all but one bucket in 10^9)
 constexpr uint32_t PB_CAP = 2048;            // LDS slots of the per-bucket sort; a fuller bucket is listed and sorted in memory (pair_bucket_big_*)
 constexpr int PB_THREADS = 256;
 constexpr uint32_t SIZE_TABLE = 1u << 20;    // direct histogram of |isize| below this; larger values are listed
@@ -89,6 +90,7 @@ __device__ __forceinline__ uint32_t pair_bucket_sorted(PairBucket &S, const uint
 // `pair`, and the caller sorts the bucket as before.
 #if defined(RSQC_WAVE_EMU)
 static unsigned long long g_k5_hashed_buckets = 0, g_k5_sorted_buckets = 0;   // (test harness: buckets paired through the set / handed to the sort)
+static unsigned char *g_k5_bucket_path = nullptr;                              // (... and, when set, per bucket: 1 = the set, 2 = handed to the sort; an empty bucket keeps its 0)
 #endif
 constexpr uint32_t PH_SLOTS = 1024;
 // (the members' second hashes and file indices ride in LDS beside their candidate numbers: two members of a slot share the 64-bit mix, so equal
@@ -103,7 +105,7 @@ __device__ __forceinline__ bool pair_bucket_hashed(PairHash &H, const uint64_t *
     const uint32_t lo = off[blockIdx.x], m = off[blockIdx.x + 1] - lo;
     if (m == 0) return true;
 #if defined(RSQC_WAVE_EMU)
-    if (threadIdx.x == 0 && m > PH_SLOTS / 2) ++g_k5_sorted_buckets;
+    if (threadIdx.x == 0 && m > PH_SLOTS / 2) { ++g_k5_sorted_buckets; if (g_k5_bucket_path) g_k5_bucket_path[blockIdx.x] = 2; }
 #endif
     if (m > PH_SLOTS / 2) return false;
     uint32_t slots = 64;
@@ -137,7 +139,7 @@ __device__ __forceinline__ bool pair_bucket_hashed(PairHash &H, const uint64_t *
         if (H.cnt[sl] == 2u && H.mh[sl][0] != H.mh[sl][1]) H.fail = 1u;   // one mix, two second hashes: two names (never seen outside crafted input)
     __syncthreads();
 #if defined(RSQC_WAVE_EMU)
-    if (threadIdx.x == 0) { if (H.fail) ++g_k5_sorted_buckets; else ++g_k5_hashed_buckets; }
+    if (threadIdx.x == 0) { if (H.fail) ++g_k5_sorted_buckets; else ++g_k5_hashed_buckets; if (g_k5_bucket_path) g_k5_bucket_path[blockIdx.x] = H.fail ? 2 : 1; }
 #endif
     if (H.fail) return false;                                              // (uniform: read behind the barrier)
     for (uint32_t sl = threadIdx.x; sl < slots; sl += PB_THREADS)

@@ -362,14 +362,48 @@ def _pairing_sorted_small():
     return Case("pairing_sorted_small", ann, ref, candidates=True, expect=dict(cands=cands, hashed=0, sorted=1, oversize=0, bins=bins, fragments=3))
 
 
-CANDIDATE_LEVEL = ["pairing_plain", "pairing_collisions", "pairing_oversize", "pairing_sorted_small"]
+def _pairing_buckets(name, fills, seed):
+    """Names of two candidates (one of one where a fill is odd) steered into buckets by the high words of their hashes (tests/k5_cases.py
+    restates the bucket rule): fills = {bucket: candidates}.  gc_replay_kernel and gc_replay_big_kernel are copies of the fragment-size
+    replay over the same pairing helpers; these are the fills at which those helpers change path."""
+    from tests import k5_cases
+    ann, ref = _pairing_reference()
+    r = np.random.default_rng(seed)
+    n = sum(fills.values())
+    nb = k5_cases.n_buckets(n)
+    cands = []
+    for b, m in fills.items():
+        qs = k5_cases.names_in_bucket(r, nb, b, (m + 1) // 2)
+        for k, q in enumerate(int(x) for x in qs):
+            h2 = int(r.integers(0, 1 << 32))
+            cands += [_random_candidate(r, q, h2) for _ in range(2 if 2 * k + 1 < m else 1)]
+    assert len(cands) == n
+    hashed = sum(1 for m in fills.values() if m <= 512)
+    return Case(name, ann, ref, candidates=True, expect=dict(cands=_number_files(r, cands), buckets=nb, hashed=hashed, sorted=len(fills) - hashed,
+                                                             oversize=sum(1 for m in fills.values() if m > 2048)))
+
+
+def _pairing_edges():
+    """512 / 513: the set at its limit and one beyond (the sort); 2 048 / 2 049: the LDS sort without a padding slot and one beyond (listed);
+    two listed buckets that are neighbours (their sorts lie side by side in big_idx); 65 listed buckets: one more than gc_replay_big_kernel
+    has workgroups."""
+    many = {b: 2049 for b in list(range(0, 320, 5)) + [346]}
+    many[171] = 347 * 384 - 65 * 2049
+    return [_pairing_buckets("pairing_buckets_of_512_and_513", {0: 512, 1: 513, 2: 127}, 512),
+            _pairing_buckets("pairing_buckets_of_2048_and_2049", {2: 2048, 7: 2049, 10: 127}, 2048),
+            _pairing_buckets("pairing_two_neighbouring_listed_buckets", {4: 2049, 5: 2049, 9: 126}, 4098),
+            _pairing_buckets("pairing_65_listed_buckets", many, 65)]
+
+
+PAIRING_EDGES = ["pairing_buckets_of_512_and_513", "pairing_buckets_of_2048_and_2049", "pairing_two_neighbouring_listed_buckets", "pairing_65_listed_buckets"]
+CANDIDATE_LEVEL = ["pairing_plain", "pairing_collisions", "pairing_oversize", "pairing_sorted_small"] + PAIRING_EDGES
 
 
 @functools.lru_cache(maxsize=None)
 def _all():
     out = {}
     for c in (_bit_ranges(), _contig_lengths(), _alphabet(), _exon_ends(), _fragment_ends(), _bin_edges(), _state_machine(), _state_machine(legacy=True),
-              *_pairing_collisions(), _pairing_oversize(), _pairing_sorted_small()):
+              *_pairing_collisions(), _pairing_oversize(), _pairing_sorted_small(), *_pairing_edges()):
         out[c.name] = c
     assert sorted(out) == sorted(WHOLE_PATH + CANDIDATE_LEVEL)
     return out

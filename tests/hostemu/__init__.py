@@ -125,6 +125,11 @@ def run_k1(params, ann, batch, grid=2, want_cov=False, slow_kernel=True, coarse=
         raise RuntimeError("k1emu rc=%d" % rc)
     o.read_length = rl.value
     o.n_overflow = int(stats[0]); o.n_listed = int(stats[1]) & 0xFFFFFFFF; o.n_deferred = int(stats[1]) >> 32; o.n_pairs = int(stats[2]); o.n_coarse = int(stats[3]) if bed is None else 0; o.n_candidates = int(stats[3]) if bed is not None else 0
+    if bed is not None:                                         # the candidates the kernel left, in file order (columns as K5_COLUMNS)
+        cols = [np.zeros(max(o.n_candidates, 1), dt) for dt in (np.uint64, np.uint64, np.uint32, np.int32, np.int32, np.uint32)]
+        lib.k1emu_last_candidates.argtypes = [C.c_void_p] * 6
+        lib.k1emu_last_candidates(*[c.ctypes.data for c in cols])
+        o.candidates = dict(zip(("file_index", "qhash", "h2", "interval", "endpos", "flag_size"), (c[:o.n_candidates] for c in cols)))
     lib.k1emu_uniform_calls.restype = C.c_ulonglong
     o.n_uniform = int(lib.k1emu_uniform_calls())
     lib.k1emu_ucache_hits.restype = C.c_ulonglong
@@ -278,7 +283,7 @@ _K5SO = os.path.join(_HERE, "libk5emu.so")
 
 def build_k5():
     csrc = os.path.join(_ROOT, "rnaseqc_amd", "csrc")
-    srcs = [os.path.join(_HERE, "k5_emu.cpp"), os.path.join(_HERE, "wavemu.h")] + [os.path.join(csrc, f) for f in ("rsqc_k5.h", "rsqc_device.h", "rsqc_read.h")]
+    srcs = [os.path.join(_HERE, "k5_emu.cpp"), os.path.join(_HERE, "wavemu.h")] + [os.path.join(csrc, f) for f in ("rsqc_k5.h", "rsqc_k5_plan.h", "rsqc_device.h", "rsqc_read.h")]
     if not os.path.exists(_K5SO) or any(os.path.getmtime(_K5SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-unused-function",
                                "-Wno-unused-variable", srcs[0], "-o", _K5SO])
@@ -294,3 +299,75 @@ def run_k5(seed, n_names, max_samples, hot=0):
     rc = lib.k5emu_run(seed, n_names, max_samples, hot, stats.ctypes.data)
     run_k5.last_paths = (int(stats[5]), int(stats[6]))          # buckets paired through the LDS set / handed to the sort (pair_bucket_hashed)
     return (rc,) + tuple(int(x) for x in stats[:5])
+
+
+K5_COLUMNS = ("file_index", "qhash", "h2", "interval", "endpos", "flag_size")
+_K5_DTYPES = (np.uint64, np.uint64, np.uint32, np.int32, np.int32, np.uint32)
+K5_PATHS = ("empty", "set", "sort", "listed")                  # the path codes of k5_emu.cpp, per bucket
+
+
+def _k5_lib():
+    lib = C.CDLL(build_k5())
+    lib.k5emu_run_cands.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_uint64]
+    lib.k5emu_partition.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    lib.k5emu_info.argtypes = [C.c_void_p]; lib.k5emu_info.restype = None
+    lib.k5emu_fetch.argtypes = [C.c_int, C.c_void_p]; lib.k5emu_fetch.restype = None
+    return lib
+
+
+def _k5_collect(lib, rc, full):
+    o = Out()
+    info = np.zeros(12, np.uint64)
+    lib.k5emu_info(info.ctypes.data)
+    o.rc = rc
+    o.n, o.n_buckets, o.n_samples, o.n_kept, o.top, o.n_beyond, o.n_pairs = (int(x) for x in info[:7])
+    o.error = int(info[7].astype(np.int64)); o.big0 = int(info[8]); o.state = (int(info[9]), int(info[10])); o.n_table_pairs = int(info[11])
+
+    def fetch(what, count, dt):
+        a = np.zeros(max(count, 1), dt)
+        lib.k5emu_fetch(what, a.ctypes.data)
+        return a[:count]
+    if rc == 0 and o.n:
+        o.count = fetch(0, o.n_buckets, np.uint32).astype(np.int64); o.off = fetch(1, o.n_buckets + 1, np.uint32).astype(np.int64)
+        o.listed = np.sort(fetch(2, min(o.big0, 1024), np.uint32).astype(np.int64)); o.perm = fetch(11, o.n, np.uint32).astype(np.int64)
+        if full:
+            o.path = fetch(3, o.n_buckets, np.uint8).astype(np.int64)
+            o.raw = sorted(zip(fetch(4, o.n_samples, np.uint64).tolist(), fetch(5, o.n_samples, np.uint32).tolist()))
+            o.kept = sorted(zip(fetch(6, o.n_kept, np.uint64).tolist(), fetch(7, o.n_kept, np.uint32).tolist()))
+            o.beyond = fetch(8, o.n_beyond, np.uint32).tolist()
+            o.pairs = list(zip(fetch(9, o.n_pairs, np.uint32).tolist(), fetch(10, o.n_pairs, np.uint32).tolist()))
+    return o
+
+
+def run_k5_cands(columns, max_samples, seed=0):
+    """The fragment-size KERNELS (rsqc_k5.h) over candidate columns given by the caller (K5_COLUMNS, emission order), launched by the
+    library's own plan (rsqc_k5_plan.h); seed: wavemu.h's seeded schedule (0: round-robin).  Returns an Out: rc (0, or 1100 + k: a guard
+    entry behind an array was written), error (the device error word), count / off per bucket, listed (bucket numbers, sorted), path per
+    bucket (index into K5_PATHS), raw and kept samples as sorted (file index, size) lists, state (the select's prefix and remaining rank),
+    top, beyond (the sizes of 2^20 and more, ascending), pairs [(size, count)] as the host merges them, n_table_pairs, perm."""
+    lib = _k5_lib()
+    cols = [np.ascontiguousarray(columns[f], dt) for f, dt in zip(K5_COLUMNS, _K5_DTYPES)]
+    n = len(cols[0])
+    assert all(len(c) == n for c in cols)
+    rc = lib.k5emu_run_cands(*[c.ctypes.data for c in cols], n, int(max_samples), int(seed))
+    return _k5_collect(lib, rc, True)
+
+
+def run_k5_partition(qhash, seed=0):
+    """pair_bucket_count / scan / scatter alone: rc, error, count, off, listed, big0 (the scan's own count of listed buckets), perm."""
+    lib = _k5_lib()
+    q = np.ascontiguousarray(qhash, np.uint64)
+    rc = lib.k5emu_partition(q.ctypes.data, len(q), int(seed))
+    return _k5_collect(lib, rc, False)
+
+
+K5_PROGRAM_SOURCE = os.path.join(_HERE, "k5_emu.cpp")          # with -DK5EMU_MAIN: a stand-alone program over a case file
+
+
+def write_k5_case_file(path, columns, max_samples, seed=0, partition_only=False):
+    """the case file the stand-alone program reads (k5_emu.cpp: main)"""
+    cols = [np.ascontiguousarray(columns[f], dt) for f, dt in zip(K5_COLUMNS, _K5_DTYPES)]
+    with open(path, "wb") as f:
+        f.write(np.array([len(cols[0]), max_samples, seed, 1 if partition_only else 0], np.uint64).tobytes())
+        for c in cols:
+            f.write(c.tobytes())

@@ -11,7 +11,7 @@ from rnaseqc_amd import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _SO = os.path.join(_HERE, "libgcemu.so")
-_HEADERS = ("rsqc_gc.h", "rsqc_k5.h", "rsqc_device.h", "rsqc_read.h", "rsqc_index.h", "rsqc_wave.h", "rsqc_k1s.h")
+_HEADERS = ("rsqc_gc.h", "rsqc_k5.h", "rsqc_k5_plan.h", "rsqc_device.h", "rsqc_read.h", "rsqc_index.h", "rsqc_wave.h", "rsqc_k1s.h")
 
 GC_BINS = 100
 CAND_COLUMNS = ("file_index", "qhash", "h2", "row", "endpos", "flag_lq", "tid")

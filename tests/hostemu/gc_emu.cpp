@@ -177,11 +177,11 @@ EMU_API int gcemu_run(const rsqc_params *p, const rsqc_annotation *a, const rsqc
     g_k5_hashed_buckets = 0; g_k5_sorted_buckets = 0;
     if (n == 0) return 0;                                                              // (run_gc_content)
     const GcCandidates c{S.file.data(), S.q.data(), S.row.data(), S.end.data(), S.fl.data(), S.tid.data(), nullptr, n, S.h2.data()};
-    const uint32_t nb = std::max<uint32_t>(1u, n / PB_MEAN);
+    const uint32_t nb = k5_bucket_count(n);                                             // (rsqc_k5_plan.h: the library's own rule)
     std::vector<uint32_t> count(nb + 1, 0u), off(nb + 1, 0xDEADu), cursor(nb + 1, 0xDEADu), perm((size_t)n + 1, 0xFFFFFFFFu), big_list(PB_BIG_MAX + 1, 0xDEADu),
         big_idx(2 * (size_t)n + 16, 0xDEADu);
     big_list[0] = 0u;
-    const uint32_t G = (n + 255) / 256;
+    const uint32_t G = k5_part_grid(n);
     launch(G, 256, [&]() { pair_bucket_count_kernel(c.qhash, n, nb, count.data()); });
     launch(1, 1024, [&]() { pair_bucket_scan_kernel(count.data(), nb, off.data(), cursor.data(), big_list.data(), &error); });
     launch(G, 256, [&]() { pair_bucket_scatter_kernel(c.qhash, n, nb, cursor.data(), perm.data()); });
@@ -189,7 +189,7 @@ EMU_API int gcemu_run(const rsqc_params *p, const rsqc_annotation *a, const rsqc
     std::vector<unsigned long long> dbins((size_t)RSQC_GC_BINS + 2, 0ull);
     dbins[(size_t)RSQC_GC_BINS + 1] = kPoison64;
     launch(nb, PB_THREADS, [&]() { gc_replay_kernel(c, off.data(), perm.data(), R, dbins.data()); });
-    launch(64, 1024, [&]() { gc_replay_big_kernel(c, off.data(), perm.data(), big_list.data(), big_idx.data(), R, dbins.data()); });
+    launch(K5_BIG_GRID, 1024, [&]() { gc_replay_big_kernel(c, off.data(), perm.data(), big_list.data(), big_idx.data(), R, dbins.data()); });
     if (dbins[(size_t)RSQC_GC_BINS + 1] != kPoison64) return 2006;
     for (int i = 0; i <= RSQC_GC_BINS; ++i) bins[i] = dbins[(size_t)i];
     stats[1] = g_k5_hashed_buckets; stats[2] = g_k5_sorted_buckets; stats[3] = big_list[0]; stats[4] = (uint64_t)(int64_t)error; stats[5] = nb;

@@ -79,6 +79,12 @@ int k1emu_overflow_script(uint32_t start, const uint64_t *masks, const uint32_t 
     return error;
 }
 
+// the candidates of the last --bed run, in file order: file index, name hash, second hash, BED row, end position, flag_size
+namespace { struct LastCand { uint64_t file, q; uint32_t h2; int32_t name, end; uint32_t fs; }; std::vector<LastCand> g_last_cands; }
+extern "C" __attribute__((visibility("default")))
+void k1emu_last_candidates(uint64_t *file, uint64_t *q, uint32_t *h2, int32_t *name, int32_t *end, uint32_t *fs) {
+    for (size_t k = 0; k < g_last_cands.size(); ++k) { const LastCand &c = g_last_cands[k]; file[k] = c.file; q[k] = c.q; h2[k] = c.h2; name[k] = c.name; end[k] = c.end; fs[k] = c.fs; }
+}
 // returns 0, an RSQC_ERR_* code, or 1000 + k for a failed internal check k
 extern "C" __attribute__((visibility("default")))
 int k1emu_run_bed(const rsqc_params *p, const rsqc_annotation *a, const rsqc_batch *b, const rsqc_bed *bed, int grid, int slow_kernel,
@@ -347,6 +353,7 @@ int k1emu_run_bed(const rsqc_params *p, const rsqc_annotation *a, const rsqc_bat
     *read_length = (int32_t)rl;
     if (cov_out) memcpy(cov_out, cov.data(), hx.cov_entries * 4);
     uint64_t n_cand = 0;
+    g_last_cands.clear();
     if (getenv("K1EMU_TRACE")) fprintf(stderr, "k1emu: reached the candidate check\n");
     if (bed) {                                                             // the kernel's candidates against the per-record rule, no shortcut
         std::map<uint64_t, size_t> got;                                    // record index -> slot
@@ -374,6 +381,7 @@ int k1emu_run_bed(const rsqc_params *p, const rsqc_annotation *a, const rsqc_bat
             const uint32_t sz = (uint32_t)(r.isize < 0 ? -(int64_t)r.isize : (int64_t)r.isize);
             if (fr_name[sl] != name || fr_end[sl] != rc2.endpos || fr_qhash[sl] != r.qhash || fr_fs[sl] != ((sz & 0x7FFFFFFFu) | (fok ? 0x80000000u : 0u)) ||
                 fr_h2[sl] != (b->qhash2 ? b->qhash2[i] : 0u)) return 1024;
+            g_last_cands.push_back(LastCand{fr_file[sl], fr_qhash[sl], fr_h2[sl], fr_name[sl], fr_end[sl], fr_fs[sl]});
         }
     }
     stats[0] = n_overflow; stats[1] = listed | (n_deferred << 32); stats[2] = n_pairs; stats[3] = bed ? n_cand : g_k1e_coarse_hits;

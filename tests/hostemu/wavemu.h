@@ -90,7 +90,10 @@ inline void run_block(int n_threads, const std::function<void()> &body) {
     blk.n_threads = n_threads; blk.body = body;
     blk.lanes.resize((size_t)n_threads); blk.waves.resize((size_t)((n_threads + kWave - 1) / kWave));
     cur_block() = &blk;
-    constexpr size_t kStack = 256 * 1024;
+#ifndef WAVEMU_STACK_BYTES
+#define WAVEMU_STACK_BYTES (256 * 1024)         /* (a sanitizer build may ask for less: its swapcontext clears the stack's shadow at every switch) */
+#endif
+    constexpr size_t kStack = WAVEMU_STACK_BYTES;
     for (int t = 0; t < n_threads; ++t) {
         LaneState &L = blk.lanes[(size_t)t];
         L.stack = (char *)malloc(kStack);

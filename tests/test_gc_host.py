@@ -106,6 +106,8 @@ def test_candidate_level_case(name, seed):
     assert int(want_bins.sum()) + want_oob > 0
     assert 1 <= got["hashed"] + got["sorted"] <= got["buckets"]                       # (an empty bucket takes neither path)
     _check_expectation(c, got)
+    if "buckets" in c.expect:
+        assert got["buckets"] == c.expect["buckets"]
     if "sorted_min" in c.expect:
         assert got["sorted"] >= c.expect["sorted_min"] and got["oversize"] == 0
 
