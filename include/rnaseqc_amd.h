@@ -743,6 +743,42 @@ RSQC_API int rsqc_track_end(rsqc_ctx *ctx, rsqc_track_info *out);
 RSQC_API int rsqc_track_rows(rsqc_ctx *ctx, uint64_t first, uint64_t n, const int32_t **tid, const uint32_t **start, const uint32_t **end, const uint32_t **depth);
 RSQC_API int rsqc_track_text(rsqc_ctx *ctx, uint64_t first, uint64_t n, const char **text, uint64_t *bytes);
 
+/* ---- coverage along the gene body, 5' to 3' (additive to ABI 6) ----------------------------------------------------------
+ * Behind rsqc_track_end the track's array holds the depth of every reference position; rsqc_genebody_end walks every gene's
+ * model positions in transcript order and sums the depth into RSQC_GENEBODY_BINS bins per gene, in one kernel at the end of the
+ * pass (no per-read kernel and no launch of a pass without the calls changes).  The contract, in integers:
+ *   model        a gene's model is a list of segments (tid, start, end), 0-based with end exclusive.  All segments of one gene
+ *                lie on one contig of the track and inside [0, length[tid]).  They are non-empty, ascending and disjoint;
+ *                abutting segments are allowed.  Each gene carries one `reverse` byte.  A gene may have zero segments.  L is
+ *                the sum of the segment lengths.
+ *   coordinate   for a model position p, u is the number of model bases in front of it in genomic order; t = u for a forward
+ *                gene, t = L - 1 - u for a `reverse` gene; bin(p) = floor(t * 100 / L), computed with a 64-bit product.
+ *   sums         sum[g][k] is the total of depth(p) over the positions of gene g with bin(p) = k: uint64_t and exact.  depth is
+ *                the track's: population and CIGAR rules are those of rsqc_track_*, nothing here re-defines them.  Genes with
+ *                L < 100 are not measured: their 100 sums are 0.  Genes that share positions each see the full depth.
+ *   info         n_genes; n_measured: genes with L >= 100; model_bases: the sum of L over measured genes; depth_sum: the sum
+ *                of all bins; bins_ms: HIP events around the stage.
+ * The sums do not depend on record order, on how the input is cut into batches, or on RSQC_TRACK_MERGE.
+ * rsqc_genebody_begin: behind rsqc_track_begin of the same pass and before the pass's first submit (RSQC_ERR_ARG otherwise).  It
+ * validates the model rules (a violation is RSQC_ERR_ARG with a message that names the gene and the rule), builds the launch plan
+ * on the host -- every measured gene's [0, L) cut into items of at most 4096 model bases, so that the work is balanced by bases --
+ * and uploads model and plan; a device refusal is RSQC_ERR_CAPACITY with the sizes.  Memory beyond the track's: 800 bytes per
+ * gene, 12 bytes per segment, 24 bytes per item of the plan.  rsqc_genebody_end: behind rsqc_track_end (RSQC_ERR_ARG otherwise);
+ * a second call returns the same figures without device work; a failure voids the pass until rsqc_reset, as with
+ * rsqc_track_end.  rsqc_genebody_sums: the n * 100 values of genes [first_gene, first_gene + n), behind rsqc_genebody_end; the
+ * host array is owned by the context and valid until its next call.  rsqc_reset, rsqc_clear_inputs and rsqc_destroy end the
+ * mode; rsqc_reset keeps the allocations.  Not exchanged by rsqc_reduce_* / rsqc_group_*.                                       */
+#define RSQC_GENEBODY_BINS 100
+typedef struct rsqc_genebody_info {
+    uint64_t n_genes, n_measured, model_bases, depth_sum;
+    double bins_ms;
+} rsqc_genebody_info;
+RSQC_API int rsqc_genebody_begin(rsqc_ctx *ctx, int32_t n_genes, const uint32_t *seg_off /*[n_genes+1]*/,
+                                 const int32_t *seg_tid, const uint32_t *seg_start, const uint32_t *seg_end,
+                                 const uint8_t *reverse /*[n_genes]*/);
+RSQC_API int rsqc_genebody_end(rsqc_ctx *ctx, rsqc_genebody_info *out);
+RSQC_API int rsqc_genebody_sums(rsqc_ctx *ctx, uint32_t first_gene, uint32_t n, const uint64_t **sums);
+
 RSQC_API const char *rsqc_strerror(int code);
 RSQC_API const char *rsqc_last_error(rsqc_ctx *ctx);
 RSQC_API const char *rsqc_counter_name(int counter);   /* the reference's Metrics key  */

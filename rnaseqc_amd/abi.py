@@ -206,6 +206,13 @@ class TrackInfo(C.Structure):
                 ("events_ms", C.c_double), ("scan_ms", C.c_double), ("rows_ms", C.c_double)]
 
 
+GENEBODY_BINS = 100
+
+
+class GenebodyInfo(C.Structure):
+    _fields_ = [("n_genes", C.c_uint64), ("n_measured", C.c_uint64), ("model_bases", C.c_uint64), ("depth_sum", C.c_uint64), ("bins_ms", C.c_double)]
+
+
 def ptr(a: np.ndarray | None):
     """numpy array -> void* (None -> NULL).  The caller keeps `a` alive."""
     if a is None:

@@ -53,6 +53,7 @@ struct Options {
     int gpus = 0;                      // --gpus (extension): GPUs to shard the BAM over by contig; 0 = RSQC_GPUS or 1
     std::string bam_list; bool has_bam_list = false;   // --bam-list (extension): a cohort, the positionals are `gtf output`
     bool bedgraph = false;             // --bedgraph (extension): the per-base coverage track, <sample>.coverage.bedgraph (rsqc_track_begin / _end / _text)
+    bool gene_body = false;            // --gene-body (extension): coverage along the gene body in 100 bins, <sample>.gene_body.tsv (rsqc_genebody_begin / _end / _sums; turns the track on)
     bool junctions = false;            // --junctions (extension): reads per splice junction, <sample>.junctions.tsv (rsqc_junctions_begin / rsqc_junctions_end)
     bool mark_duplicates = false;      // --mark-duplicates (extension, implies --sort): flag 0x400 rewritten on the GPU before the records are counted (rsqc_markdup_begin / rsqc_markdup_end)
     bool sort = false;                 // --sort (extension): input in any order, put in coordinate order on the GPU (rsqc_sort_begin / rsqc_sort_end)
@@ -91,7 +92,8 @@ void usage(std::ostream &o) {
          "      --sort                            (extension) Accept input in any order: the records are put in coordinate order on the GPU before they are counted\n"
          "      --mark-duplicates                 (extension) Flag duplicate fragments on the GPU before they are counted: implies --sort, replaces the input's 0x400 flags (one GPU, one input)\n"
          "      --junctions                       (extension) Count reads per splice junction on the GPU and write [sample].junctions.tsv (one GPU)\n"
-         "      --bedgraph                        (extension) Build the per-base coverage track on the GPU and write [sample].coverage.bedgraph (one GPU; needs LN in the header)\n";
+         "      --bedgraph                        (extension) Build the per-base coverage track on the GPU and write [sample].coverage.bedgraph (one GPU; needs LN in the header)\n"
+         "      --gene-body                       (extension) Sum the coverage along every gene's body, 5' to 3' in 100 bins, on the GPU and write [sample].gene_body.tsv (one GPU; needs LN in the header)\n";
 }
 
 long to_long(const std::string &flag, const std::string &v) {
@@ -174,6 +176,7 @@ Options parse(int argc, char **argv) {
         else if (name == "mark-duplicates") o.mark_duplicates = o.sort = true;
         else if (name == "junctions") o.junctions = true;
         else if (name == "bedgraph") o.bedgraph = true;
+        else if (name == "gene-body") o.gene_body = true;
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
         else if (name == "detection-threshold") o.detection = to_ulong(name, need());
         else throw ParseError("Flag could not be matched: " + name);
@@ -511,6 +514,8 @@ struct Session {
     std::string prefix;
     bool async_reports = false;
     JunctionIndex junction_index;                      // --junctions: the annotation's exon boundaries, built once
+    GeneBodyModel gene_body; bool gene_body_built = false;      // --gene-body: the model for the header in use (its contigs and their lengths)
+    std::vector<uint64_t> gene_body_lengths;
     std::future<void> report_job;
     void finish_reports() { if (report_job.valid()) report_job.get(); }
 };
@@ -594,6 +599,7 @@ void flatten_for(Session &S, Annotation &ann, const std::vector<std::string> &co
     if (S.flattened) { ann.chrom_id = S.base_chrom_id; ann.chrom_name = S.base_chrom_name; }   // as a run of this input alone sees chromosomeMap
     ann.flatten(contigs);
     S.contigs = contigs; S.flattened = true;
+    S.gene_body_built = false;
 }
 
 // what the report writer reads of rsqc_results, in memory of its own: the vectors behind rsqc_results are the context's and
@@ -677,11 +683,13 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     if (sam_input && o.verbosity > 1) cout << "Input: " << input_format_name(in.fmt) << " (" << bam_contigs.size() << " @SQ lines), parsed on the GPU" << endl;
     if (o.verbosity > 1) cout << "Checking bam header..." << endl;
     if (!shares_contigs(S, ann, bam_contigs)) { cerr << S.prefix << "BAM file shares no contigs with GTF" << endl; return 11; }
-    if (o.bedgraph)                                    // the track needs every contig's length
+    if (o.bedgraph || o.gene_body)                     // the track needs every contig's length
         for (size_t k = 0; k < bam_contigs.size(); ++k)
-            if (k >= in.lengths.size() || in.lengths[k] == 0) { cerr << S.prefix << "--bedgraph needs the length (LN) of every contig in the header: none for " << bam_contigs[k] << endl; return 10; }
+            if (k >= in.lengths.size() || in.lengths[k] == 0) { cerr << S.prefix << (o.bedgraph ? o.gene_body ? "--bedgraph and --gene-body need" : "--bedgraph needs" : "--gene-body needs") << " the length (LN) of every contig in the header: none for " << bam_contigs[k] << endl; return 10; }
     const bool same_header = S.flattened && bam_contigs == S.contigs;
     if (!same_header) flatten_for(S, ann, bam_contigs);
+    // --gene-body: the model of this header's contigs and lengths, built when either changes
+    if (o.gene_body && (!S.gene_body_built || S.gene_body_lengths != in.lengths)) { S.gene_body.build(ann, in.lengths); S.gene_body_lengths = in.lengths; S.gene_body_built = true; }
     const int n_ref_bam = (int)bam_contigs.size();
 
     // ---- the context and its inputs
@@ -790,10 +798,17 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     // --junctions: every batch the per-read kernels run leaves its junction instances on the device (under --sort: the sorted batches)
     if (o.junctions && (rc = rsqc_junctions_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --bedgraph: and its coverage events, in a difference array over the header's contigs (kept by the context while it is large enough)
-    if (o.bedgraph) {
+    if (o.bedgraph || o.gene_body) {
         std::vector<const char *> track_names;
         for (auto &nm : bam_contigs) track_names.push_back(nm.c_str());
         if ((rc = rsqc_track_begin(gpu, n_ref_bam, in.lengths.data(), track_names.data())) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    }
+    // --gene-body: the model of this header's contigs (built when the header changes), checked, planned and uploaded
+    if (o.gene_body) {
+        const GeneBodyModel &m = S.gene_body;
+        if ((rc = rsqc_genebody_begin(gpu, (int32_t)m.reverse.size(), m.seg_off.data(), m.seg_tid.data(), m.seg_start.data(), m.seg_end.data(), m.reverse.data())) != RSQC_OK) {
+            cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10;
+        }
     }
     if (sam_input) {
         // ---- SAM text: the host reads the file (plain) or frames its BGZF blocks, the device does the rest
@@ -893,8 +908,16 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     rsqc_junction_table junctions{};
     if (o.junctions && rc == RSQC_OK) rc = rsqc_junctions_end(gpu, &junctions);       // (ordered and reduced inside the timed window: the price of the flag)
     rsqc_track_info track{};
-    if (o.bedgraph && rc == RSQC_OK) rc = rsqc_track_end(gpu, &track);                // (scan and rows inside the timed window as well)
+    if ((o.bedgraph || o.gene_body) && rc == RSQC_OK) rc = rsqc_track_end(gpu, &track);      // (scan and rows inside the timed window as well)
+    rsqc_genebody_info gene_body{};
+    GeneBodyProfile gene_body_rows;
+    if (o.gene_body && rc == RSQC_OK) rc = rsqc_genebody_end(gpu, &gene_body);               // (and the stage over the scanned array)
     S.t_loop1 = Clock::now();
+    if (o.gene_body && rc == RSQC_OK) {
+        // the report's part, like the track's text: the sums come from the context in one window and are folded into the file's 100 rows
+        const uint64_t *sums = nullptr;
+        if ((rc = rsqc_genebody_sums(gpu, 0, (uint32_t)gene_body.n_genes, &sums)) == RSQC_OK) gene_body_rows = gene_body_profile(S.gene_body, sums);
+    }
     if (rc == RSQC_ERR_BAD_CIGAR) throw std::invalid_argument("Unrecognized Cigar Op ");
     if (rc == RSQC_ERR_EMPTY_MEDIAN) throw std::range_error("Cannot compute median of an empty list");
     if (rc != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
@@ -912,6 +935,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (o.bedgraph)
             cout << "Track: population " << track.population << ", aligned_bases " << track.aligned_bases << ", clipped_bases " << track.clipped_bases << ", rows " << track.n_rows
                  << ", events_ms " << track.events_ms << ", scan_ms " << track.scan_ms << ", rows_ms " << track.rows_ms << endl;
+        if (o.gene_body)
+            cout << "Gene body: genes " << gene_body.n_genes << ", measured " << gene_body.n_measured << ", eligible " << gene_body_rows.eligible << ", model_bases " << gene_body.model_bases
+                 << ", depth_sum " << gene_body.depth_sum << ", bins_ms " << gene_body.bins_ms << endl;
         cout << "Estimating library complexity..." << endl;
         cout << "Generating report" << endl;
     }
@@ -928,6 +954,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (rc != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
         if (io_failed) { cerr << S.prefix << "Filesystem error:  cannot write " << out_dir << "/" << sample.name << ".coverage.bedgraph" << endl; return 8; }
         if (o.verbosity) cout << "Track text: rows " << track.n_rows << ", bytes " << bytes << ", seconds " << secs << endl;
+    }
+    if (o.gene_body && !write_gene_body(out_dir + "/" + sample.name + ".gene_body.tsv", gene_body_rows)) {
+        cerr << S.prefix << "Filesystem error:  cannot write " << out_dir << "/" << sample.name << ".gene_body.tsv" << endl; return 8;
     }
     if (!S.async_reports) {
         S.t_rep0 = Clock::now();
@@ -1241,6 +1270,12 @@ int main(int argc, char **argv) {
             bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
             if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
             if (many_gpus) throw ValidationError("--bedgraph runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
+        }
+        if (o.gene_body) {
+            // the stage reads ONE context's difference array, like --bedgraph
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--gene-body runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
         }
         if (o.junctions) {
             // one table per context: the per-contig tables of shards would only need concatenating, but that path is not built

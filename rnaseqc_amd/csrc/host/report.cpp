@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdio>
 #include <fstream>
 #include <functional>
 #include <iostream>
@@ -417,6 +418,71 @@ void write_junctions(const std::string &path, const Annotation &ann, const Junct
         f << '\t' << t.start[k] << '\t' << t.end[k] << '\t' << t.reads[k] << '\t' << t.hq_reads[k] << '\t' << t.max_overhang[k] << '\t'
           << (index.known(chrom, t.start[k], t.end[k]) ? 1 : 0) << NL;
     }
+}
+
+void GeneBodyModel::build(const Annotation &ann, const std::vector<uint64_t> &contig_lengths) {
+    const rsqc_annotation &a = ann.ann;
+    const size_t n = (size_t)std::max(a.n_genes_listed, 0);
+    seg_off.assign(1, 0u); seg_tid.clear(); seg_start.clear(); seg_end.clear(); gene_len.assign(n, 0u); reverse.assign(n, 0);
+    std::vector<std::pair<long long, long long>> ivs;
+    for (size_t g = 0; g < n; ++g) {
+        const uint32_t lo = a.gene_exon_off[g], hi = a.gene_exon_off[g + 1];
+        const int32_t tid = lo < hi ? a.exon_row_contig[a.gene_exon_row[lo]] : -1;
+        if (tid >= 0 && tid < a.n_ref && (size_t)tid < contig_lengths.size()) {
+            const long long ln = (long long)contig_lengths[(size_t)tid];
+            reverse[g] = (a.exon_row_flags[a.gene_exon_row[lo]] & RSQC_FF_STRAND_MASK) == RSQC_STRAND_REVERSE ? 1 : 0;
+            ivs.clear();
+            for (uint32_t k = lo; k < hi; ++k) {
+                const uint32_t r = a.gene_exon_row[k];
+                if (a.exon_row_contig[r] != tid) continue;
+                const long long s = std::max<long long>((long long)a.exon_row_start[r] - 1, 0), e = std::min<long long>(a.exon_row_end[r], ln);
+                if (s < e) ivs.emplace_back(s, e);
+            }
+            std::sort(ivs.begin(), ivs.end());
+            const size_t first = seg_start.size();
+            for (auto &iv : ivs) {
+                if (seg_start.size() > first && iv.first <= (long long)seg_end.back()) { seg_end.back() = (uint32_t)std::max<long long>(seg_end.back(), iv.second); continue; }
+                seg_tid.push_back(tid); seg_start.push_back((uint32_t)iv.first); seg_end.push_back((uint32_t)iv.second);
+            }
+            for (size_t k = first; k < seg_start.size(); ++k) gene_len[g] += seg_end[k] - seg_start[k];
+        }
+        seg_off.push_back((uint32_t)seg_start.size());
+    }
+}
+
+GeneBodyProfile gene_body_profile(const GeneBodyModel &m, const uint64_t *sums) {
+    GeneBodyProfile p;
+    double acc[RSQC_GENEBODY_BINS] = {};
+    for (size_t g = 0; g < m.gene_len.size(); ++g) {
+        const uint64_t L = m.gene_len[g];
+        if (L < RSQC_GENEBODY_BINS) continue;
+        const uint64_t *s = sums + g * RSQC_GENEBODY_BINS;
+        uint64_t total = 0;
+        for (int k = 0; k < RSQC_GENEBODY_BINS; ++k) { p.depth_sum[k] += s[k]; total += s[k]; }
+        if (total < L) continue;                           // (a mean depth below 1: a profile of a handful of reads)
+        ++p.eligible;
+        const double mean = (double)total / (double)L;
+        uint64_t edge = 0;                                 // ceil(k L / 100)
+        for (uint64_t k = 0; k < RSQC_GENEBODY_BINS; ++k) {
+            const uint64_t next = ((k + 1) * L + RSQC_GENEBODY_BINS - 1) / RSQC_GENEBODY_BINS;
+            acc[k] += ((double)s[k] / (double)(next - edge)) / mean;
+            edge = next;
+        }
+    }
+    if (p.eligible) for (int k = 0; k < RSQC_GENEBODY_BINS; ++k) p.norm_mean[k] = acc[k] / (double)p.eligible;
+    return p;
+}
+
+bool write_gene_body(const std::string &path, const GeneBodyProfile &p) {
+    std::ofstream f(path);
+    f << "bin\tdepth_sum\tgenes\tnorm_mean" << NL;
+    char buf[64];
+    for (int k = 0; k < RSQC_GENEBODY_BINS; ++k) {
+        snprintf(buf, sizeof buf, "%.6f", p.norm_mean[k]);
+        f << k << '\t' << p.depth_sum[k] << '\t' << p.eligible << '\t' << buf << NL;
+    }
+    f.close();
+    return f.good();
 }
 
 }  // namespace rsqc_host

@@ -44,4 +44,22 @@ struct JunctionIndex {
 // row of the table, in table order.  `ann` is flattened for the input's header (contig_names, chrom_of_contig).
 void write_junctions(const std::string &path, const Annotation &ann, const JunctionIndex &index, const rsqc_junction_table &table);
 
+// --gene-body: the model handed to rsqc_genebody_begin, built once per input header.  For every listed gene: its exon rows
+// (gene_exon_off / gene_exon_row of the flattened annotation) on the contig of the gene's first exon row, if the header has that
+// contig; 1-based closed -> 0-based half-open, clipped to [0, LN), overlapping and abutting rows merged; reverse: that first row's
+// strand is RSQC_STRAND_REVERSE.  (Rows parked under --legacy sit on a contig no header has.)
+struct GeneBodyModel {
+    std::vector<uint32_t> seg_off, seg_start, seg_end, gene_len;
+    std::vector<int32_t> seg_tid;
+    std::vector<uint8_t> reverse;
+    void build(const Annotation &ann, const std::vector<uint64_t> &contig_lengths);
+};
+// the file's three columns from the sums ([n_genes][RSQC_GENEBODY_BINS]): depth_sum over the measured genes (L >= 100); eligible
+// genes (L >= 100 and total depth >= L); norm_mean: the mean over the eligible genes, in gene order, of
+// (sum[g][k] / len_k) / (total_g / L) with len_k = ceil((k + 1) L / 100) - ceil(k L / 100), in doubles; 0 without an eligible gene
+struct GeneBodyProfile { uint64_t eligible = 0; uint64_t depth_sum[RSQC_GENEBODY_BINS] = {}; double norm_mean[RSQC_GENEBODY_BINS] = {}; };
+GeneBodyProfile gene_body_profile(const GeneBodyModel &model, const uint64_t *sums);
+// <output>/<sample>.gene_body.tsv: bin, depth_sum, genes, norm_mean -- 100 rows, bin 0 = the 5' end.  False: the file could not be written
+bool write_gene_body(const std::string &path, const GeneBodyProfile &profile);
+
 }  // namespace rsqc_host

@@ -173,6 +173,17 @@ struct TrackState {
     char *h_text = nullptr; size_t h_text_cap = 0;     // page-locked: the window of the last rsqc_track_text
 };
 
+// --gene-body (rsqc_genebody_begin / rsqc_genebody_end / rsqc_genebody_sums, rsqc_genebody_api.cpp): the model (12 bytes per
+// segment) and the launch plan (24 bytes per item) of the pass, the sums on the device (800 bytes per gene), one window on the host
+struct GenebodyState {
+    bool active = false, done = false;
+    int32_t n_genes = 0;
+    uint64_t n_items = 0;
+    DevBuf seg_tid, seg_start, seg_end, items, sums, total;
+    rsqc_genebody_info info{};
+    uint64_t *h_sums = nullptr; size_t h_sums_cap = 0; // page-locked, in values: the window of the last rsqc_genebody_sums
+};
+
 }  // namespace rsqc
 using namespace rsqc;            // (every unit that sees this header is host code of the library)
 
@@ -267,6 +278,7 @@ struct rsqc_ctx {
     SortState sort;
     JunctionState junc;
     TrackState track;
+    GenebodyState genebody;
     MarkdupState markdup;
 
     // host results
@@ -311,6 +323,8 @@ void junction_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forge
 // --bedgraph: the batch's coverage events added to the difference array, on the main stream (rsqc_track_api.cpp)
 int track_events(rsqc_ctx *c, const UploadedBatch *u, const DevBatch &d);
 void track_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forgets the track
+// --gene-body: the stage behind rsqc_track_end (rsqc_genebody_api.cpp)
+void genebody_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the model and the sums
 
 template <class T>
 int upload(rsqc_ctx *c, std::vector<DevBuf> &owner, const T *host, size_t n, const T **out, bool from_pool = false) {

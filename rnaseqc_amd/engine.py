@@ -82,6 +82,9 @@ def load_library():
         lib.rsqc_track_end.argtypes = [vp, C.POINTER(abi.TrackInfo)]
         lib.rsqc_track_rows.argtypes = [vp, C.c_uint64, C.c_uint64] + [C.POINTER(vp)] * 4
         lib.rsqc_track_text.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        lib.rsqc_genebody_begin.argtypes = [vp, C.c_int32] + [vp] * 5
+        lib.rsqc_genebody_end.argtypes = [vp, C.POINTER(abi.GenebodyInfo)]
+        lib.rsqc_genebody_sums.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         _lib = lib
     return _lib
 
@@ -95,6 +98,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_decode_begin", "rsqc_decode_submit", "rsqc_decode_end", "rsqc_decode_begin_sam", "rsqc_decode_submit_text",
     "rsqc_sort_begin", "rsqc_sort_end", "rsqc_markdup_begin", "rsqc_markdup_end", "rsqc_markdup_verdicts", "rsqc_junctions_begin", "rsqc_junctions_end",
     "rsqc_track_begin", "rsqc_track_end", "rsqc_track_rows", "rsqc_track_text",
+    "rsqc_genebody_begin", "rsqc_genebody_end", "rsqc_genebody_sums",
 ]
 
 
@@ -311,6 +315,29 @@ class Engine:
         p, nbytes = C.c_void_p(), C.c_uint64()
         self._check(self._l.rsqc_track_text(self._h, int(first), int(n), C.byref(p), C.byref(nbytes)))
         return C.string_at(p.value, nbytes.value) if nbytes.value else b""
+
+    # ---- coverage along the gene body (rsqc_genebody_*) ---------------------------------------------------------------
+    def genebody_begin(self, seg_off, seg_tid, seg_start, seg_end, reverse):
+        """Behind track_begin and before the first submit: the model of the pass -- gene g's segments are rows [seg_off[g],
+        seg_off[g + 1]) of (seg_tid, seg_start, seg_end), 0-based with the end exclusive; `reverse` has one byte per gene."""
+        off = np.ascontiguousarray(seg_off, dtype=np.uint32)
+        tid = np.ascontiguousarray(seg_tid, dtype=np.int32)
+        start, end = np.ascontiguousarray(seg_start, dtype=np.uint32), np.ascontiguousarray(seg_end, dtype=np.uint32)
+        rev = np.ascontiguousarray(reverse, dtype=np.uint8)
+        assert len(off) == len(rev) + 1 and len(tid) == len(start) == len(end)
+        self._check(self._l.rsqc_genebody_begin(self._h, len(rev), abi.ptr(off), abi.ptr(tid), abi.ptr(start), abi.ptr(end), abi.ptr(rev)))
+
+    def genebody_end(self) -> dict:
+        """After track_end(): the sums are built on the device; the fields of rsqc_genebody_info."""
+        info = abi.GenebodyInfo()
+        self._check(self._l.rsqc_genebody_end(self._h, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in abi.GenebodyInfo._fields_}
+
+    def genebody_sums(self, first_gene, n) -> np.ndarray:
+        """The sums of genes [first_gene, first_gene + n) as a (n, 100) uint64 array (a copy)."""
+        p = C.c_void_p()
+        self._check(self._l.rsqc_genebody_sums(self._h, int(first_gene), int(n), C.byref(p)))
+        return abi._view(p.value, int(n) * abi.GENEBODY_BINS, np.uint64).copy().reshape(int(n), abi.GENEBODY_BINS)
 
     def read_device(self, ptr, count, dtype):
         """count items of dtype from a device pointer of this context (tests): hipMemcpy of the HIP runtime the library itself is
