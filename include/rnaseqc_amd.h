@@ -473,6 +473,12 @@ RSQC_API int rsqc_device_vectors(rsqc_ctx *ctx, rsqc_device_range out[3]);
  *   the batch's transfer function as a short table: entered with state r, the batch leaves rl_state[k] for the first k
  *   in [rl_offset[b], rl_offset[b+1]) with rl_span[k] > r, and r itself when no entry qualifies.  Composing the
  *   batches of ALL shards in ascending batch_file_index from state 0 gives the reference's value.
+ *   LIMIT: the keys of a table are the prefix maxima of the alignment span over the batch's (the range's) records that reach :275, and
+ *   one batch or range holds at most 128 of them (RSQC_RL_MAXP).  Reads of ONE length need a single entry whatever their spans; with
+ *   mixed lengths every record whose span exceeds all spans before it in the batch adds one.  A batch or range beyond the limit sets
+ *   the device error word: the pass ends with RSQC_ERR_CAPACITY at the next rsqc_wait / rsqc_finalize (never with a value), and
+ *   rsqc_last_error names Read Length, the batch or range by its file index and the number 128.  rsqc_reset starts a new pass;
+ *   smaller batches (the limit is per batch, not per file) avoid it.
  *   Fragment sizes (src/Expression.cpp:482-540): mates pair inside one BED interval, hence inside one shard; the
  *   cut-off --fragment-samples applies in FILE order.  The shard hands over the samples it kept (its first N by the file
  *   index of the completing record, in no particular order); the merged histogram holds the N smallest file indices

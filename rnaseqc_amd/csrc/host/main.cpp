@@ -29,6 +29,7 @@
 #include "gtf.hpp"
 #include "report.hpp"
 #include "sam_feed.hpp"
+#include "../rsqc_rl_compose.h"
 
 using namespace rsqc_host;
 
@@ -354,22 +355,18 @@ void shard_worker(Shard &sh, const std::string &bam_path, const Options &o, int 
 struct ShardMerge { int32_t read_length = 0; std::vector<int64_t> fsize; std::vector<uint64_t> fcount; uint32_t remaining = 0; };
 
 int merge_shards(std::vector<Shard> &shards, uint32_t fragment_samples, ShardMerge &m, std::string &err) {
-    struct Item { uint64_t file; const uint32_t *span; const int32_t *state; uint32_t n; };
-    std::vector<Item> items;
+    std::vector<rsqc::RlTable> items;
     std::vector<std::pair<uint64_t, uint32_t>> samples;
     for (auto &sh : shards) {
         rsqc_shard_info si{};
         const int rc = rsqc_shard_summary(sh.gpu, &si);
         if (rc != RSQC_OK) { err = rsqc_last_error(sh.gpu); return rc; }
         for (uint32_t b = 0; b < si.n_batches; ++b)
-            items.push_back(Item{si.batch_file_index[b], si.rl_span + si.rl_offset[b], si.rl_state + si.rl_offset[b], si.rl_offset[b + 1] - si.rl_offset[b]});
+            items.push_back(rsqc::RlTable{si.batch_file_index[b], si.rl_span + si.rl_offset[b], si.rl_state + si.rl_offset[b], si.rl_offset[b + 1] - si.rl_offset[b]});
         for (uint32_t k = 0; k < si.n_samples; ++k) samples.emplace_back(si.sample_file_index[k], si.sample_size[k]);
     }
     // Read Length (src/RNASeQC.cpp:275-278): the batches of all shards in file order, each applied as its transfer function
-    std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.file < b.file; });
-    uint32_t r = 0;
-    for (auto &it : items) for (uint32_t k = 0; k < it.n; ++k) if (it.span[k] > r) { r = (uint32_t)it.state[k]; break; }
-    m.read_length = (int32_t)r;
+    m.read_length = rsqc::rl_compose(items);
     // fragment sizes (src/Expression.cpp:482-540): the --fragment-samples first samples of the union, in file order
     const size_t keep = std::min<size_t>(samples.size(), fragment_samples);
     if (keep < samples.size()) std::nth_element(samples.begin(), samples.begin() + (long)keep, samples.end());

@@ -311,6 +311,7 @@ void free_parked(rsqc_ctx *c);                 // caller: the stream has been sy
 int retire_completed(rsqc_ctx *c, bool all);
 int run_batch(rsqc_ctx *c, UploadedBatch *u);
 const char *device_error_text(int err);
+std::string device_error_message(rsqc_ctx *c, int err);      // ... naming the cause where the device left one (stream idle)
 // collecting mode: the batch's records are appended to the collection instead of being run (rsqc_sort_api.cpp)
 int sort_append(rsqc_ctx *c, UploadedBatch *u);
 void sort_drop(rsqc_ctx *c);                   // leaves the collecting mode and frees the collection (hipFree waits for the device)

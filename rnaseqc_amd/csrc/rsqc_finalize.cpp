@@ -1,5 +1,6 @@
 // rsqc_finalize.cpp -- end of file: the coverage / fragment / GC kernels, the read-back of the result vectors, shard summaries, timing.
 #include "rsqc_ctx.h"
+#include "rsqc_rl_compose.h"
 
 // The device holds every result vector in its final order (genes by listed id, exons by exon id), so the read-back
 // is ONE D2H of the arena into the page-locked mirror; the results struct points straight into the mirror.
@@ -41,7 +42,7 @@ static int read_back(rsqc_ctx *c) {
     const int err = *(const int *)(H + c->off_misc + 16);
     if (err) {
         c->sticky = err;
-        return fail(c, err, device_error_text(err));
+        return fail(c, err, device_error_message(c, err));
     }
     return 0;
 }
@@ -263,14 +264,11 @@ static void unpack_rl_summaries(rsqc_ctx *c) {           // after the stream has
 // "Read Length" of a pass that held batches of several file ranges: the summaries (one transfer function per batch or range) applied in
 // ascending file index from state 0 -- what read_length_kernel does on the device for a pass of plain batches (src/RNASeQC.cpp:275-278)
 static int32_t compose_read_length(const rsqc_ctx *c) {
-    std::vector<size_t> order(c->batch_file_index.size());
-    for (size_t k = 0; k < order.size(); ++k) order[k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return c->batch_file_index[x] < c->batch_file_index[y]; });
-    uint32_t r = 0;
-    for (size_t k : order)
-        for (uint32_t j = c->h_rl_offset[k]; j < c->h_rl_offset[k + 1]; ++j)
-            if (c->h_rl_span[j] > r) { r = (uint32_t)c->h_rl_state[j]; break; }     // the first key above the state decides (rsqc_kr.h)
-    return (int32_t)r;
+    std::vector<rsqc::RlTable> tables(c->batch_file_index.size());
+    for (size_t k = 0; k < tables.size(); ++k)
+        tables[k] = rsqc::RlTable{c->batch_file_index[k], c->h_rl_span.data() + c->h_rl_offset[k], c->h_rl_state.data() + c->h_rl_offset[k],
+                                  c->h_rl_offset[k + 1] - c->h_rl_offset[k]};
+    return rsqc::rl_compose(tables);                     // (rsqc_rl_compose.h: the loop the command line's shard merge runs too)
 }
 static void finish_finalize_bookkeeping(rsqc_ctx *c) {
     float ms = 0.f;

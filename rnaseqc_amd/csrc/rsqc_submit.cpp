@@ -1,5 +1,6 @@
 // rsqc_submit.cpp -- a batch on its way through the context: upload, buffer pools, the per-record kernels, retirement into the arenas.
 #include "rsqc_ctx.h"
+#include "rsqc_rl_compose.h"
 
 namespace rsqc {
 
@@ -7,6 +8,21 @@ const char *device_error_text(int err) {
     return err == RSQC_ERR_BAD_CIGAR ? "Unrecognized Cigar Op" :
            err == RSQC_ERR_CAPACITY ? "a device-side capacity was exceeded" :
            err == RSQC_ERR_EMPTY_MEDIAN ? "Cannot compute median of an empty list" : "device error";
+}
+// The text of a device error word.  RSQC_ERR_CAPACITY is raised by several kernels; the one limit a caller can run into with ordinary
+// input -- more than 128 prefix maxima of span in one batch or file range (read_length_kernel, rsqc_kr.h) -- is named: the kernel
+// leaves the cause in the flag word of the batch's summary slot, read here (error path only; the stream is idle), and the text is
+// rsqc_rl_compose.h's.
+std::string device_error_message(rsqc_ctx *c, int err) {
+    const size_t nb = c->batch_file_index.size();
+    if (err == RSQC_ERR_CAPACITY && nb && c->d_rl_summary.p) {
+        std::vector<uint32_t> flags(nb, 0u);
+        if (hipMemcpy2D(flags.data(), 4, (const uint32_t *)c->d_rl_summary.p + 1, (size_t)RSQC_RL_SUMMARY_WORDS * 4, 4, nb, hipMemcpyDeviceToHost) == hipSuccess) {
+            const std::string msg = rl_limit_message(flags.data(), 1, nb, c->batch_file_index.data(), c->batch_records.data());
+            if (!msg.empty()) return msg;
+        }
+    }
+    return device_error_text(err);
 }
 hipEvent_t get_event(rsqc_ctx *c) {
     if (!c->event_pool.empty()) { hipEvent_t e = c->event_pool.back(); c->event_pool.pop_back(); return e; }
@@ -134,7 +150,7 @@ static int check_device_error(rsqc_ctx *c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (err) {
         c->sticky = err;
-        return fail(c, err, device_error_text(err));
+        return fail(c, err, device_error_message(c, err));
     }
     return 0;
 }
@@ -315,23 +331,17 @@ int run_batch(rsqc_ctx *c, UploadedBatch *u) {
     if (ranges && c->dparams.legacy) return fail(c, RSQC_ERR_ARG, "rsqc_batch.seg_file_index is not supported with --legacy");
     const size_t n_entries = ranges ? u->seg_file_index.size() : 1;          // order-dependent summaries: one per batch, or one per range
     if (c->batch_file_index.size() + n_entries > kMaxBatches) return fail(c, RSQC_ERR_CAPACITY, "more than 16384 batches / file ranges in one pass");
-    if (!c->d_rl_summary.p) { int rc3 = dev_alloc(c, c->d_rl_summary, kMaxBatches * RSQC_RL_SUMMARY_WORDS * 4, false); if (rc3) return rc3; }
+    if (!c->d_rl_summary.p) { int rc3 = dev_alloc(c, c->d_rl_summary, kMaxBatches * RSQC_RL_SUMMARY_WORDS * 4, true); if (rc3) return rc3; }
     uint32_t *rl_slot = (uint32_t *)c->d_rl_summary.p + c->batch_file_index.size() * RSQC_RL_SUMMARY_WORDS;
     DevBatch d = u->d;
     d.record_base = u->file_index_base;
     acc.rl_seg = nullptr;
     if (ranges) {
-        for (size_t k = 0; k < n_entries; ++k) { c->batch_file_index.push_back(u->seg_file_index[k]); c->batch_records.push_back(u->seg_records[k]); }
-        c->next_record_base = u->seg_file_index.back() + u->seg_records.back();
-        c->have_ranges = true;
         // the per-segment Read-Length inputs, armed {max span 0, min l_qseq UINT_MAX, max l_qseq 0}
         c->h_rl_arm.resize(3 * n_entries);
         for (size_t k = 0; k < n_entries; ++k) { c->h_rl_arm[3 * k] = 0u; c->h_rl_arm[3 * k + 1] = 0xFFFFFFFFu; c->h_rl_arm[3 * k + 2] = 0u; }
         HIP_TRY(c, hipMemcpyAsync(u->rl_seg.p, c->h_rl_arm.data(), n_entries * 12, hipMemcpyHostToDevice, c->stream));
         acc.rl_seg = (uint32_t *)u->rl_seg.p;
-    } else {
-        c->batch_file_index.push_back(u->file_index_base); c->batch_records.push_back(u->n);
-        c->next_record_base = u->file_index_base + u->n;
     }
     hipEvent_t e0 = get_event(c), e1 = get_event(c);
     HIP_TRY(c, hipEventRecord(e0, c->stream));
@@ -347,6 +357,16 @@ int run_batch(rsqc_ctx *c, UploadedBatch *u) {
     if (c->have_bed && !c->dparams.legacy) launch_frag_compact(c->stream, acc.frag, frag_dense, u->n, grid);
     launch_classify_slow(c->stream, c->dann, c->dparams, d, acc);
     launch_read_length(c->stream, c->dann, c->dparams, d, acc, rl_slot);
+    // the batch's entries are listed only now that the kernel which writes their summary slots is enqueued: a submit that fails
+    // above leaves no entry whose slot -- its flag word is read by device_error_message -- was never written in this pass
+    if (ranges) {
+        for (size_t k = 0; k < n_entries; ++k) { c->batch_file_index.push_back(u->seg_file_index[k]); c->batch_records.push_back(u->seg_records[k]); }
+        c->next_record_base = u->seg_file_index.back() + u->seg_records.back();
+        c->have_ranges = true;
+    } else {
+        c->batch_file_index.push_back(u->file_index_base); c->batch_records.push_back(u->n);
+        c->next_record_base = u->file_index_base + u->n;
+    }
     if (c->have_ref && !c->dparams.legacy) {          // --fasta: fragment GC candidates, a separate pass over the batch
         GcBuf *gbp = nullptr; if (int rc2 = acquire_gc(c, u->n, &gbp)) return rc2;
         GcBuf &gb = *gbp;

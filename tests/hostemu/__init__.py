@@ -59,7 +59,7 @@ def build_k1(coarse=True):
     csrc = os.path.join(_ROOT, "rnaseqc_amd", "csrc")
     so = _K1SO if coarse else _K1SO_DEFAULT
     srcs = [os.path.join(_HERE, "k1_emu.cpp"), os.path.join(_HERE, "wavemu.h")] + \
-           [os.path.join(csrc, f) for f in ("rsqc_read.h", "rsqc_index.h", "rsqc_k1.h", "rsqc_k1s.h", "rsqc_kr.h", "rsqc_k4.h", "rsqc_wave.h", "rsqc_device.h")] + \
+           [os.path.join(csrc, f) for f in ("rsqc_read.h", "rsqc_index.h", "rsqc_k1.h", "rsqc_k1s.h", "rsqc_kr.h", "rsqc_rl_compose.h", "rsqc_k4.h", "rsqc_wave.h", "rsqc_device.h")] + \
            [os.path.join(_ROOT, "include", "rnaseqc_amd.h")]
     # (RSQC_EMU_DEFS="-DK1E_..." : the emulation of an A/B build of the kernel; remove the .so files before and after)
     if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in srcs):
@@ -371,3 +371,72 @@ def write_k5_case_file(path, columns, max_samples, seed=0, partition_only=False)
         f.write(np.array([len(cols[0]), max_samples, seed, 1 if partition_only else 0], np.uint64).tobytes())
         for c in cols:
             f.write(c.tobytes())
+
+
+RL_SUMMARY_WORDS, RL_MAXP = 2 + 2 * 128, 128                   # RSQC_RL_SUMMARY_WORDS (rsqc_device.h), RSQC_RL_MAXP (rsqc_kr.h)
+RL_POISON = 0xA5A5A5A5
+K1_PROGRAM_SOURCE = os.path.join(_HERE, "k1_emu.cpp")          # with -DK1EMU_MAIN: a stand-alone program over KR case files
+
+
+def run_kr(params, ann, batch, grid=2, r_in=0, ranges=False, coarse=True):
+    """The Read-Length stage under the emulation (k1_emu.cpp: k1emu_run_kr): the per-record kernels produce tile_span and the extremes, then
+    read_length_kernel (rsqc_kr.h) runs from the entry state `r_in`, or -- ranges=True, a batch of Batch.concat_ranges -- with rl_seg armed
+    as the library arms it and one block per segment.  Returns an Out: rc (0, an RSQC_ERR_* code, 1000 + k: an internal check of the
+    harness), error (the device error word), tile_span, extremes [entries, 3] (max span, min l_qseq, max l_qseq), per entry P, flags and
+    the table (keys, states), untouched (True when every summary word behind entry P, and the guard slot behind the last entry, still holds
+    the poison), state (the kernel's final state; for ranges: the slots composed in file order from 0 by rsqc_rl_compose.h)."""
+    lib = C.CDLL(build_k1(coarse))
+    lib.k1emu_run_kr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    a, b = ann.to_struct(), batch.to_struct()
+    entries = len(batch.seg_tid) if ranges else 1
+    tile_span = np.zeros(max((batch.n + 63) // 64, 1), np.uint32); extremes = np.zeros(3 * max(entries, 1), np.uint32)
+    summary = np.full((entries + 1) * RL_SUMMARY_WORDS, RL_POISON, np.uint32); info = np.zeros(2, np.int32)
+    o = Out()
+    o.rc = lib.k1emu_run_kr(C.addressof(params), C.addressof(a), C.addressof(b), int(grid), int(r_in), 1 if ranges else 0, tile_span.ctypes.data,
+                            extremes.ctypes.data, summary.ctypes.data, info.ctypes.data)
+    o.state, o.error = int(info[0]), int(info[1])
+    o.tile_span = tile_span[:(batch.n + 63) // 64].astype(np.int64); o.extremes = extremes[:3 * entries].reshape(entries, 3).astype(np.int64)
+    slots = summary.reshape(entries + 1, RL_SUMMARY_WORDS)
+    o.P = [int(s[0]) for s in slots[:entries]]; o.flags = [int(s[1]) for s in slots[:entries]]
+    o.tables = [([int(x) for x in s[2:2 + 2 * min(P, RL_MAXP):2]], [int(x) for x in s[3:3 + 2 * min(P, RL_MAXP):2].astype(np.int32)]) for s, P in zip(slots, o.P)]
+    # what rsqc_last_error says of these slots (rsqc_rl_compose.h: rl_limit_message, the text rsqc_submit.cpp hands on); "": none is flagged
+    lib.k1emu_rl_limit_message.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32]
+    lib.k1emu_rl_limit_message.restype = C.c_uint32
+    fi = np.ascontiguousarray(batch.seg_file_index if ranges else [batch.file_index_base], np.uint64)
+    nrec = np.ascontiguousarray(np.diff(batch.seg_start.astype(np.int64)) if ranges else [batch.n], np.uint64)
+    buf = C.create_string_buffer(1024)
+    lib.k1emu_rl_limit_message(summary.ctypes.data, entries, fi.ctypes.data, nrec.ctypes.data, buf, 1024)
+    o.message = buf.value.decode()
+    o.untouched = bool((slots[entries] == RL_POISON).all()) and all(bool((s[2 + 2 * min(P, RL_MAXP):] == RL_POISON).all()) for s, P in zip(slots, o.P))
+    return o
+
+
+def rl_compose(items):
+    """rsqc_rl_compose.h, the loop rsqc_finalize.cpp and the command line's shard merge run: items = [(file index, keys, states)], any order."""
+    lib = C.CDLL(build_k1(True))
+    lib.k1emu_rl_compose.argtypes = [C.c_void_p] * 4 + [C.c_uint32]
+    lib.k1emu_rl_compose.restype = C.c_int32
+    fi = np.array([t[0] for t in items] + [0], np.uint64)
+    off = np.concatenate([[0], np.cumsum([len(t[1]) for t in items])]).astype(np.uint32)
+    span = np.array([x for t in items for x in t[1]] + [0], np.uint32); state = np.array([x for t in items for x in t[2]] + [0], np.int32)
+    return int(lib.k1emu_rl_compose(fi.ctypes.data, off.ctypes.data, span.ctypes.data, state.ctypes.data, len(items)))
+
+
+def write_kr_case_file(path, params, ann, batch, grid=2, r_in=0, ranges=False):
+    """the case file the stand-alone program reads (k1_emu.cpp: main): a header, then length-prefixed arrays in the order of the structs"""
+    ann.to_struct(); batch.to_struct()                          # (leave the contiguous arrays of the boundary on the objects)
+    blobs = [bytes(params), np.array([ann.n_ref, ann.n_contigs, ann.n_genes, ann.n_genes_listed, ann.n_exons], np.int32).tobytes()]
+    for f in ("gene_row_contig", "gene_row_start", "gene_row_end", "gene_row_flags", "gene_row_id", "exon_row_contig", "exon_row_start", "exon_row_end",
+              "exon_row_flags", "exon_row_id", "exon_row_gene", "gene_is_globin", "gene_exon_off", "gene_exon_row", "gene_row_order", "exon_row_order"):
+        v = getattr(ann, f)
+        blobs.append(b"" if v is None else np.ascontiguousarray(v).tobytes())
+    blobs.append(np.array([batch.n, batch.file_index_base, len(batch.cigar), len(batch.seg_tid), len(batch.wide_index)], np.uint64).tobytes())
+    blobs += [batch._core.tobytes(), batch._aux.tobytes()]
+    blobs += [getattr(batch, f).tobytes() for f in ("cigar", "seg_tid", "seg_start", "wide_index", "wide_nm", "wide_l_qseq", "wide_n_cigar")]
+    blobs.append(b"" if batch.qhash2 is None else batch.qhash2.tobytes())
+    blobs.append(b"" if batch.seg_file_index is None else batch.seg_file_index.tobytes())
+    assert len(blobs) == 30
+    with open(path, "wb") as f:
+        f.write(np.array([grid, r_in, 1 if ranges else 0], np.uint64).tobytes())
+        for bl in blobs:
+            f.write(np.array([len(bl)], np.uint64).tobytes()); f.write(bl)

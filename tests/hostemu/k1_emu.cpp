@@ -20,6 +20,7 @@
 #include "../../rnaseqc_amd/csrc/rsqc_k1.h"
 #include "../../rnaseqc_amd/csrc/rsqc_k1s.h"
 #include "../../rnaseqc_amd/csrc/rsqc_kr.h"
+#include "../../rnaseqc_amd/csrc/rsqc_rl_compose.h"
 #define RSQC_FIN_STAMP(sec)
 #define RSQC_FIN_SECT(base, sec)
 #define RSQC_FIN_BEGIN
@@ -37,6 +38,21 @@ struct SlowAccH {
     void exon_add(uint32_t row, double f) { (*exon_rows)[row] += f; }
     void cov_range(uint32_t cidx, uint32_t len) { if (!len) return; (*cov)[cidx] += 1u; (*cov)[cidx + len] -= 1u; }
 };
+}  // namespace
+
+// ---- KR under test (k1emu_run_kr below): what the Read-Length part of k1emu_run_bed takes from and hands to the caller.  Without a
+// request (every other entry point) that part runs as it always did: state 0 in, no rl_seg, one block, the final state checked.
+namespace {
+struct KrRequest {
+    uint32_t r_in;            // the context's state when the batch arrives (plain batches; a batch of ranges is composed from 0)
+    int ranges;               // the batch is several file ranges (rsqc_batch.seg_file_index): rl_seg armed as rsqc_submit.cpp arms it, a block per segment
+    uint32_t *tile_span;      // [(n + 63) / 64] out
+    uint32_t *extremes;       // [3 * entries] out: rl_stats (plain) or rl_seg (ranges) as the per-record kernels left them
+    uint32_t *summary;        // [(entries + 1) * RSQC_RL_SUMMARY_WORDS] in / out: the caller's poison in, the slots out (one guard slot behind)
+    int32_t state;            // out: the state the kernel left (plain) / the slots composed in file order by rsqc_rl_compose.h (ranges)
+    int error;                // out: the device error word behind read_length_kernel
+};
+KrRequest *g_kr = nullptr;
 }  // namespace
 
 extern "C" __attribute__((visibility("default"))) unsigned long long k1emu_uniform_calls() { return g_k1e_uniform_calls; }
@@ -150,6 +166,8 @@ int k1emu_run_bed(const rsqc_params *p, const rsqc_annotation *a, const rsqc_bat
     db.n = n; db.record_base = b->file_index_base; db.core = core.data(); db.aux = aux.data(); db.cigar = cigar.data();
     db.n_seg = b->n_seg; db.seg_tid = b->seg_tid; db.seg_start = b->seg_start;
     db.n_wide = b->n_wide; db.wide_index = b->wide_index; db.wide_nm = b->wide_nm; db.wide_l_qseq = b->wide_l_qseq; db.wide_n_cigar = b->wide_n_cigar;
+    const bool kr_ranges = g_kr && g_kr->ranges;
+    if (kr_ranges) { if (!b->seg_file_index || !b->n_seg) return RSQC_ERR_ARG; db.seg_file_index = b->seg_file_index; }
 
     const size_t G = (size_t)a->n_genes, E = (size_t)a->n_exons;
     std::vector<unsigned long long> u64(3 * G + RSQC_N_COUNTERS + 1, 0ull);
@@ -167,7 +185,10 @@ int k1emu_run_bed(const rsqc_params *p, const rsqc_annotation *a, const rsqc_bat
     std::vector<uint32_t> defer_index((size_t)n + 64, 0xDEFE0000u), defer_list((size_t)n + 64 * (size_t)grid + 64, 0xDEFE0001u); uint32_t defer_total = 0;
     std::vector<uint32_t> tile_span((size_t)((n + 63) / 64) + 64 * (size_t)total_waves + 64, 0xABCDu);
     std::vector<uint32_t> rl_stats = {0u, 0xFFFFFFFFu, 0u};
-    int32_t rl_state = 0; int error = 0;
+    int32_t rl_state = g_kr && !kr_ranges ? (int32_t)g_kr->r_in : 0; int error = 0;
+    // a batch of ranges: the per-segment inputs, armed {max span 0, min l_qseq UINT_MAX, max l_qseq 0} (rsqc_submit.cpp)
+    std::vector<uint32_t> rl_seg;
+    if (kr_ranges) for (uint32_t s = 0; s < b->n_seg; ++s) { rl_seg.push_back(0u); rl_seg.push_back(0xFFFFFFFFu); rl_seg.push_back(0u); }
     DevAccum acc{};
     acc.gene_reads = u64.data(); acc.gene_unique = acc.gene_reads + G; acc.gene_frag = acc.gene_unique + G; acc.counters = acc.gene_frag + G;
     acc.exon_acc = exon_acc.data(); acc.cov_diff = cov.data();
@@ -184,6 +205,7 @@ int k1emu_run_bed(const rsqc_params *p, const rsqc_annotation *a, const rsqc_bat
     acc.frag.flag_size = fr_fs.data(); acc.frag.h2 = fr_h2.data(); acc.frag.chunk_count = fr_counts.data(); acc.frag.count = nullptr; acc.frag.cap = (uint32_t)n;
     acc.tile_span = tile_span.data();
     acc.rl_stats = rl_stats.data(); acc.read_length = &rl_state; acc.error = &error;
+    acc.rl_seg = kr_ranges ? rl_seg.data() : nullptr;
 
     const K1Args A{d, dp, db, acc};
     g_k1e_args = &A; g_k1e_coarse_hits = 0; g_k1e_uniform_calls = 0; g_k1e_ucache_hits = 0; g_k1e_uniform2_calls = 0;
@@ -287,28 +309,59 @@ int k1emu_run_bed(const rsqc_params *p, const rsqc_annotation *a, const rsqc_bat
         }
     }
     // ---- Read-Length inputs: tile maxima and batch extremes against the per-record values; the state machine itself ---
-    uint32_t rl = 0, smax = 0, lmin = 0xFFFFFFFFu, lmax = 0;
+    uint32_t rl = (uint32_t)rl_state, smax = 0, lmin = 0xFFFFFFFFu, lmax = 0;
     {
         std::vector<uint32_t> want((size_t)((n + 63) / 64), 0u);
+        std::vector<uint32_t> want_seg(rl_seg.size());
+        for (size_t k = 0; k < want_seg.size(); ++k) want_seg[k] = k % 3 == 1 ? 0xFFFFFFFFu : 0u;
+        uint32_t sg = 0;
         for (uint64_t i = 0; i < n; ++i) {
             Record r;
             if (!load(i, r)) return RSQC_ERR_ARG;
             RecordCounters rc2; bool hq; uint32_t aligned; Blocks B;
             gate_cascade(d, dp, r, rc2, hq, aligned, B);
             if (rc2.error) return rc2.error;
+            while (kr_ranges && sg + 1 < b->n_seg && b->seg_start[sg + 1] <= i) ++sg;
             if (rc2.rl_eligible) {
                 want[(size_t)(i >> 6)] = std::max(want[(size_t)(i >> 6)], rc2.rl_span);
                 smax = std::max(smax, rc2.rl_span); lmin = std::min(lmin, (uint32_t)rc2.rl_lqseq); lmax = std::max(lmax, (uint32_t)rc2.rl_lqseq);
                 if (rc2.rl_span > rl) rl = (uint32_t)rc2.rl_lqseq;
+                if (kr_ranges) {
+                    uint32_t *ws = want_seg.data() + 3 * (size_t)sg;
+                    ws[0] = std::max(ws[0], rc2.rl_span); ws[1] = std::min(ws[1], (uint32_t)rc2.rl_lqseq); ws[2] = std::max(ws[2], (uint32_t)rc2.rl_lqseq);
+                }
             }
         }
         // per-wave ranges are multiples of 64 records, so a wave's tile t is batch tile (wbeg / 64 + t)
         for (size_t t = 0; t < want.size(); ++t) if (tile_span[t] != want[t]) return 1006;
-        if (rl_stats[0] != smax || rl_stats[1] != lmin || rl_stats[2] != lmax) return 1007;
-        // the Read-Length KERNEL: the batch's transfer function applied to state 0 must leave the value of the walk above
-        std::vector<uint32_t> summary(RSQC_RL_SUMMARY_WORDS + 8, 0u);
+        if (kr_ranges) { if (rl_seg != want_seg) return 1014; }              // (the batch-level extremes are not kept for a batch of ranges)
+        else if (rl_stats[0] != smax || rl_stats[1] != lmin || rl_stats[2] != lmax) return 1007;
+        const uint32_t entries = kr_ranges ? b->n_seg : 1u;
+        if (g_kr) {
+            for (size_t t = 0; t < want.size(); ++t) g_kr->tile_span[t] = tile_span[t];
+            for (uint32_t k = 0; k < 3u * entries; ++k) g_kr->extremes[k] = kr_ranges ? rl_seg[k] : rl_stats[k];
+        }
+        // the Read-Length KERNEL: the batch's transfer function applied to the entry state must leave the value of the walk above
+        // (a batch of ranges: a block per segment, a slot each, composed by the product's own loop in file order from state 0)
+        std::vector<uint32_t> own_summary(g_kr ? 0 : RSQC_RL_SUMMARY_WORDS + 8, 0u);
+        uint32_t *const summary = g_kr ? g_kr->summary : own_summary.data();
+        wavemu::grid_dim().x = entries;
+        for (uint32_t k = 0; k < entries; ++k) {
+            wavemu::block_idx().x = k;
+            wavemu::run_block(64, [&]() { read_length_kernel(d, dp, db, acc, summary); });
+        }
         wavemu::grid_dim().x = 1; wavemu::block_idx().x = 0;
-        wavemu::run_block(64, [&]() { read_length_kernel(d, dp, db, acc, summary.data()); });
+        if (kr_ranges) {
+            std::vector<std::vector<uint32_t>> keys(entries); std::vector<std::vector<int32_t>> vals(entries);
+            std::vector<RlTable> tables;
+            for (uint32_t k = 0; k < entries; ++k) {
+                const uint32_t *w = summary + (size_t)k * RSQC_RL_SUMMARY_WORDS;
+                for (uint32_t j = 0; j < std::min<uint32_t>(w[0], RSQC_RL_MAXP); ++j) { keys[k].push_back(w[2 + 2 * j]); vals[k].push_back((int32_t)w[3 + 2 * j]); }
+                tables.push_back(RlTable{b->seg_file_index[k], keys[k].data(), vals[k].data(), (uint32_t)keys[k].size()});
+            }
+            rl_state = rl_compose(tables);
+        }
+        if (g_kr) { g_kr->state = rl_state; g_kr->error = error; }
         if (error) return error;
         if ((uint32_t)rl_state != rl) return 1009;
     }
@@ -387,3 +440,99 @@ int k1emu_run_bed(const rsqc_params *p, const rsqc_annotation *a, const rsqc_bat
     stats[0] = n_overflow; stats[1] = listed | (n_deferred << 32); stats[2] = n_pairs; stats[3] = bed ? n_cand : g_k1e_coarse_hits;
     return 0;
 }
+
+// ---- the Read-Length stage on its own terms (tests/test_kr_edges_host.py): the same run as k1emu_run -- every check above holds --
+// with an entry state or as a batch of file ranges, and with the kernel's inputs and raw summary slots handed back.
+// summary: (entries + 1) * RSQC_RL_SUMMARY_WORDS words, filled by the caller (a poison pattern: words the kernel does not own must come
+// back as they went in); entries = 1, or n_seg for ranges.  info[0] = the final state, info[1] = the device error word.
+extern "C" __attribute__((visibility("default")))
+int k1emu_run_kr(const rsqc_params *p, const rsqc_annotation *a, const rsqc_batch *b, int grid, uint32_t r_in, int ranges,
+                 uint32_t *tile_span, uint32_t *extremes, uint32_t *summary, int32_t *info /*[2]*/) {
+    const size_t G = (size_t)std::max(a->n_genes, 1), E = (size_t)std::max(a->n_exons, 1);
+    std::vector<uint64_t> counters(RSQC_N_COUNTERS), gr(G), gu(G), gf(G); std::vector<double> ex(E);
+    int32_t rl = 0; uint64_t stats[4] = {0, 0, 0, 0};
+    KrRequest rq{r_in, ranges, tile_span, extremes, summary, 0, 0};
+    g_kr = &rq;
+    const int rc = k1emu_run_bed(p, a, b, nullptr, grid, 1, counters.data(), gr.data(), gu.data(), gf.data(), ex.data(), &rl, nullptr, stats);
+    g_kr = nullptr;
+    info[0] = rq.state; info[1] = rq.error;
+    return rc;
+}
+// rsqc_rl_compose.h as the product calls it: tables k = (span, state)[offset[k] : offset[k + 1]] at file_index[k], any order
+extern "C" __attribute__((visibility("default")))
+int32_t k1emu_rl_compose(const uint64_t *file_index, const uint32_t *offset, const uint32_t *span, const int32_t *state, uint32_t n) {
+    std::vector<RlTable> tables;
+    for (uint32_t k = 0; k < n; ++k) tables.push_back(RlTable{file_index[k], span + offset[k], state + offset[k], offset[k + 1] - offset[k]});
+    return rl_compose(tables);
+}
+
+// the message rsqc_last_error gives for a pass that ended on the limit of 128 prefix maxima (rsqc_rl_compose.h: rl_limit_message), from raw
+// summary slots as k1emu_run_kr hands them back; returns its length (0: no slot is flagged)
+extern "C" __attribute__((visibility("default")))
+uint32_t k1emu_rl_limit_message(const uint32_t *summary, uint32_t entries, const uint64_t *file_index, const uint64_t *records, char *out, uint32_t cap) {
+    const std::string msg = rl_limit_message(summary + 1, RSQC_RL_SUMMARY_WORDS, entries, file_index, records);
+    if (cap) { const size_t m = std::min<size_t>(msg.size(), cap - 1); memcpy(out, msg.data(), m); out[m] = 0; }
+    return (uint32_t)msg.size();
+}
+
+#ifdef K1EMU_MAIN
+// A stand-alone program over case files (tests/hostemu/__init__.py: write_kr_case_file), so that the harness and the kernels run under the
+// host sanitizers without anything sanitized inside Python.  Prints one line per file: rc, error, state, and per slot P and the flag word;
+// `guard` counts the words behind entry P of any slot (and of the guard slot) that no longer hold the poison.
+#include <cstdio>
+#include <memory>
+namespace {
+// (every array in an allocation of exactly its size: a read one entry past it is the sanitizer's to report)
+struct Blob { std::unique_ptr<unsigned char[]> store; size_t bytes = 0; template <class T> const T *as() const { return bytes ? reinterpret_cast<const T *>(store.get()) : nullptr; } };
+bool read_blob(FILE *f, Blob &bl) {
+    uint64_t nb = 0;
+    if (fread(&nb, 8, 1, f) != 1) return false;
+    bl.bytes = (size_t)nb; bl.store.reset(new unsigned char[(size_t)nb ? (size_t)nb : 1]);
+    return nb == 0 || fread(bl.store.get(), 1, (size_t)nb, f) == (size_t)nb;
+}
+}  // namespace
+int main(int argc, char **argv) {
+    const uint32_t POISON = 0xA5A5A5A5u;
+    for (int f_i = 1; f_i < argc; ++f_i) {
+        FILE *f = fopen(argv[f_i], "rb");
+        if (!f) { fprintf(stderr, "cannot open %s\n", argv[f_i]); return 2; }
+        uint64_t head[3];                                              // grid, entry state, ranges
+        if (fread(head, 8, 3, f) != 3) return 2;
+        Blob bl[30];
+        for (int k = 0; k < 30; ++k) if (!read_blob(f, bl[k])) { fprintf(stderr, "short case file %s\n", argv[f_i]); return 2; }
+        fclose(f);
+        if (bl[0].bytes != sizeof(rsqc_params) || bl[1].bytes != 20 || bl[18].bytes != 40) return 2;
+        const rsqc_params *p = bl[0].as<rsqc_params>();
+        const int32_t *an = bl[1].as<int32_t>();
+        rsqc_annotation a{};
+        a.n_ref = an[0]; a.n_contigs = an[1]; a.n_genes = an[2]; a.n_genes_listed = an[3]; a.n_exons = an[4];
+        a.gene_row_contig = bl[2].as<int32_t>(); a.gene_row_start = bl[3].as<int32_t>(); a.gene_row_end = bl[4].as<int32_t>();
+        a.gene_row_flags = bl[5].as<uint8_t>(); a.gene_row_id = bl[6].as<uint32_t>();
+        a.exon_row_contig = bl[7].as<int32_t>(); a.exon_row_start = bl[8].as<int32_t>(); a.exon_row_end = bl[9].as<int32_t>();
+        a.exon_row_flags = bl[10].as<uint8_t>(); a.exon_row_id = bl[11].as<uint32_t>(); a.exon_row_gene = bl[12].as<uint32_t>();
+        a.gene_is_globin = bl[13].as<uint8_t>(); a.gene_exon_off = bl[14].as<uint32_t>(); a.gene_exon_row = bl[15].as<uint32_t>();
+        a.gene_row_order = bl[16].as<uint32_t>(); a.exon_row_order = bl[17].as<uint32_t>();
+        const uint64_t *bn = bl[18].as<uint64_t>();
+        rsqc_batch b{};
+        b.n = bn[0]; b.file_index_base = bn[1]; b.n_cigar_total = bn[2]; b.n_seg = (uint32_t)bn[3]; b.n_wide = (uint32_t)bn[4];
+        b.core = bl[19].as<rsqc_rec_core>(); b.aux = bl[20].as<rsqc_rec_aux>(); b.cigar = bl[21].as<uint32_t>();
+        b.seg_tid = bl[22].as<int32_t>(); b.seg_start = bl[23].as<uint64_t>();
+        b.wide_index = bl[24].as<uint64_t>(); b.wide_nm = bl[25].as<int32_t>(); b.wide_l_qseq = bl[26].as<int32_t>(); b.wide_n_cigar = bl[27].as<uint32_t>();
+        b.qhash2 = bl[28].as<uint32_t>(); b.seg_file_index = bl[29].as<uint64_t>();
+        const uint32_t entries = head[2] ? b.n_seg : 1u;
+        std::vector<uint32_t> tile_span((size_t)((b.n + 63) / 64)), extremes(3 * (size_t)entries), summary((size_t)(entries + 1) * RSQC_RL_SUMMARY_WORDS, POISON);
+        int32_t info[2] = {0, 0};
+        const int rc = k1emu_run_kr(p, &a, &b, (int)head[0], (uint32_t)head[1], (int)head[2], tile_span.data(), extremes.data(), summary.data(), info);
+        printf("k1emu_kr rc=%d error=%d state=%d entries=%u", rc, info[1], info[0], entries);
+        uint64_t touched = 0;
+        for (uint32_t k = 0; k <= entries; ++k) {
+            const uint32_t *w = summary.data() + (size_t)k * RSQC_RL_SUMMARY_WORDS;
+            const uint32_t from = k < entries ? 2u + 2u * std::min<uint32_t>(w[0], RSQC_RL_MAXP) : 0u;
+            if (k < entries) printf(" P%u=%u:%u", k, w[0], w[1]);
+            for (uint32_t j = from; j < RSQC_RL_SUMMARY_WORDS; ++j) touched += w[j] != POISON;
+        }
+        printf(" guard=%llu\n", (unsigned long long)touched);
+    }
+    return 0;
+}
+#endif
