@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define RSQC_ABI_VERSION 6
+#define RSQC_ABI_VERSION 7
 
 #if defined(__GNUC__)
 #define RSQC_API __attribute__((visibility("default")))
@@ -327,6 +327,15 @@ typedef struct rsqc_batch {
        one kernel launch; the order-dependent outputs are then kept per segment (rsqc_shard_summary lists one entry per segment
        instead of one per batch) and the context's own "Read Length" is composed from them in file order.  Since ABI version 4.  */
     const uint64_t *seg_file_index;    /* [n_seg]                              */
+
+    /* optional (may be NULL): the UMI key of every record (rsqc_umi_pack of its UMI; 0 = no usable UMI).  Since ABI version 7.  Read ONLY
+       in a pass that collects for UMI-aware duplicate marking (rsqc_markdup_use_umi, below): everywhere else the column is ignored
+       and never dereferenced.  In such a pass it is ALL OR NONE like qhash2, with the difference that it must be there: a batch
+       without the column is RSQC_ERR_ARG and leaves the collection as it was.  Both ingest paths of the library fill it when
+       rsqc_decode_params.umi_source selects a source (the host reader: --umi-tag / --umi-qname); rsqc_decode_window.device_batch.umi
+       then points at the window's column.  It stays in the collection (8 bytes per record): the sorted output batches do not
+       carry it.                                                                                                              */
+    const uint64_t *umi;               /* [n]                                  */
 } rsqc_batch;
 
 /* ---- results ---------------------------------------------------------------- */
@@ -545,6 +554,9 @@ typedef struct rsqc_bgzf_block {
  * INFLATED bytes in `compressed`, in_bytes == out_bytes, the CRC-32 has been checked.  Such blocks form one run at the
  * END of a call's table, their bytes one after the other in `compressed`.                                          */
 #define RSQC_BGZF_INFLATED 1u
+#define RSQC_UMI_SOURCE_NONE  0
+#define RSQC_UMI_SOURCE_TAG   1
+#define RSQC_UMI_SOURCE_QNAME 2
 typedef struct rsqc_decode_params {
     int32_t n_ref;                     /* reference sequences in the BAM header                                */
     int32_t has_chimeric_tag;          /* --chimeric-tag (readStringTag, src/RNASeQC.cpp:780-800)              */
@@ -554,7 +566,13 @@ typedef struct rsqc_decode_params {
     int32_t  pipelined;                /* 1: a call returns once its kernels are enqueued; the NEXT call (or rsqc_decode_end)
                                           completes it, so `out` then describes the call before -- the next chunk of the
                                           file crosses PCIe beside this call's kernels                            */
-    int32_t  reserved;
+    /* ABI 7 (the four bytes that were `reserved`): where a record's UMI comes from.  RSQC_UMI_SOURCE_NONE: the windows get no umi
+       column -- it is neither allocated nor written, no kernel changes.  _TAG: the FIRST aux field named umi_tag of type Z (BAM: the
+       bytes up to its NUL; SAM: the text behind XX:Z:); another type, no such field, or one cut off by a malformed aux tail is key 0.
+       _QNAME: the bytes of QNAME behind its last umi_sep; no separator, or nothing behind it, is key 0.                         */
+    uint8_t  umi_source;
+    char     umi_tag[2];
+    char     umi_sep;
     uint64_t reserve_inflated_bytes;   /* 0, or: size the device buffers at rsqc_decode_begin for calls of up to this many
                                           inflated bytes (they grow on demand otherwise, which costs a re-allocation
                                           of every window buffer each time a larger call arrives)                 */
@@ -680,6 +698,31 @@ RSQC_API int rsqc_markdup_begin(rsqc_ctx *ctx);
 RSQC_API int rsqc_markdup_end(rsqc_ctx *ctx, rsqc_markdup_info *out);
 RSQC_API int rsqc_markdup_verdicts(rsqc_ctx *ctx, uint64_t first, uint64_t n, const uint8_t **dup);
 
+/* ---- UMI-aware duplicate marking (ABI 7) --------------------------------------------------------------------------------------
+ * rsqc_markdup_use_umi makes the pass's marking UMI-aware.  The contract is the one above with ONE change: the signature of an anchor
+ * becomes (tid, u5, rev, mrev, kind, w, umi), umi being the anchor RECORD's own key in rsqc_batch.umi (rsqc_umi_pack); the mate's key is
+ * never consulted.  Anchors with key 0 (no usable UMI) form sets among themselves: an anchor without a UMI is never a duplicate of one
+ * that has one.  Survivor, verdicts and the name rule are unchanged.  tests/markdup_umi_ref.py is the executable form.
+ *   limits       UMIs match exactly (no grouping of UMIs one mismatch apart); only the anchor's UMI counts; a UMI has at most 31 bases;
+ *                an N (any byte other than A C G T in either case and the joiners - and +) voids the UMI: key 0.
+ * rsqc_markdup_use_umi: behind rsqc_markdup_begin and before the pass's first submit (RSQC_ERR_ARG otherwise).  Every batch of the
+ * pass must then carry rsqc_batch.umi (see there).  rsqc_markdup_umi_end: behind rsqc_sort_end of such a pass (RSQC_ERR_ARG otherwise);
+ * a second call returns the same figures.  position_duplicate_fragments is what the marking WITHOUT the UMI would have called on
+ * the same collection (anchors minus distinct position signatures): beside rsqc_markdup_info.duplicate_fragments it says how many
+ * fragments the UMIs rescued.  rsqc_markdup_info and rsqc_markdup_end are as without the mode.
+ * Order and memory: the anchors are sorted by (K_hi, K_lo >> 8, umi, 255 - mapq, arrival) -- LSD in four stages: the mapq byte, the
+ * live digits of the UMI keys, K_lo above its mapq byte, K_hi; dead digit positions are skipped in all of them.  The collection holds
+ * 8 more bytes per record (the umi column: 52 instead of 44), the stage 8 more bytes per anchor (the anchors' keys: 52 instead of 44);
+ * both go with the stage's other buffers before the coordinate sort allocates, and the sorted output batches never see the column.
+ * rsqc_reset, rsqc_clear_inputs and rsqc_destroy end the mode.                                                                   */
+typedef struct rsqc_markdup_umi_info {
+    uint64_t anchors_with_umi;         /* anchors whose key is not 0                                                  */
+    uint64_t anchors_without_umi;
+    uint64_t position_duplicate_fragments;
+} rsqc_markdup_umi_info;
+RSQC_API int rsqc_markdup_use_umi(rsqc_ctx *ctx);
+RSQC_API int rsqc_markdup_umi_end(rsqc_ctx *ctx, rsqc_markdup_umi_info *out);
+
 /* ---- reads per splice junction (additive to ABI 6) ---------------------------------------------------------------------
  * Between rsqc_junctions_begin and the end of the pass every batch that the per-read kernels run also leaves its splice-junction
  * INSTANCES on the device (one extra kernel per batch; no other kernel, output or launch changes), and rsqc_junctions_end orders
@@ -796,6 +839,10 @@ RSQC_API uint64_t rsqc_qname_hash(const char *name, size_t len);
 /* the second hash of a name (rsqc_batch.qhash2): a multiply-xorshift recurrence with its own constants + the murmur3 fmix32
  * finaliser over (state ^ length); it shares no structure with the FNV-1a of rsqc_qname_hash                                  */
 RSQC_API uint32_t rsqc_qname_hash2(const char *name, size_t len);
+/* the UMI key (rsqc_batch.umi): A C G T in either case are 2 bits each, the first base most significant; - and + are skipped; the
+ * key is (1 << 2L) | bits for L bases, so A, AA and AAA differ and no usable UMI gives 0; 0 = no usable UMI: nothing left, any
+ * other byte (N included) or more than 31 bases.  Exact, not a hash.                                                          */
+RSQC_API uint64_t rsqc_umi_pack(const char *umi, uint32_t len);
 
 #ifdef __cplusplus
 }

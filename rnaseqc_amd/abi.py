@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import numpy as np
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # error codes
 OK, ERR_ARG, ERR_HIP, ERR_BAD_CIGAR, ERR_CAPACITY, ERR_NO_DEVICE, ERR_EMPTY_MEDIAN, ERR_INPUT = 0, -1, -2, -3, -4, -5, -6, -7
@@ -128,6 +128,7 @@ class BatchStruct(C.Structure):
         ("qname_off", _P), ("qname", _P),
         ("qhash2", _P),
         ("seg_file_index", _P),
+        ("umi", _P),                                  # ABI 7: read only in a pass behind rsqc_markdup_use_umi
     ]
 
 
@@ -140,8 +141,12 @@ class BgzfBlock(C.Structure):
 
 class DecodeParams(C.Structure):
     _fields_ = [("n_ref", C.c_int32), ("has_chimeric_tag", C.c_int32), ("chimeric_tag", C.c_char * 2),
-                ("filter_tag", (C.c_char * 2) * MAX_FILTER_TAGS), ("file_index_base", C.c_uint64), ("pipelined", C.c_int32), ("reserved", C.c_int32),
+                ("filter_tag", (C.c_char * 2) * MAX_FILTER_TAGS), ("file_index_base", C.c_uint64), ("pipelined", C.c_int32),
+                ("umi_source", C.c_uint8), ("umi_tag", C.c_char * 2), ("umi_sep", C.c_char),      # ABI 7: the four bytes that were `reserved`
                 ("reserve_inflated_bytes", C.c_uint64)]
+
+
+UMI_SOURCE_NONE, UMI_SOURCE_TAG, UMI_SOURCE_QNAME = 0, 1, 2
 
 
 class DecodeWindow(C.Structure):
@@ -193,6 +198,10 @@ class SortInfo(C.Structure):
 class MarkdupInfo(C.Structure):
     _fields_ = [("records", C.c_uint64), ("population", C.c_uint64), ("anchors", C.c_uint64), ("sets", C.c_uint64), ("duplicate_fragments", C.c_uint64),
                 ("flagged_records", C.c_uint64), ("cleared_records", C.c_uint64), ("sig_ms", C.c_double), ("sort_ms", C.c_double), ("mark_ms", C.c_double)]
+
+
+class MarkdupUmiInfo(C.Structure):
+    _fields_ = [("anchors_with_umi", C.c_uint64), ("anchors_without_umi", C.c_uint64), ("position_duplicate_fragments", C.c_uint64)]
 
 
 class JunctionTable(C.Structure):
@@ -320,3 +329,30 @@ def qname_hash2_bytes(names: np.ndarray) -> np.ndarray:
 
 def qname_hash2(name: bytes) -> int:
     return int(qname_hash2_bytes(np.frombuffer(name, dtype=np.uint8)[None, :])[0])
+
+
+UMI_MAX_BASES = 31
+
+
+def umi_pack(umi: bytes) -> int:
+    """rsqc_umi_pack: A C G T in either case are 2 bits each, the first base most significant; - and + are skipped; the key is
+    (1 << 2L) | bits for L bases; 0 = no usable UMI (nothing left, any other byte, more than 31 bases)."""
+    bits, n = 0, 0
+    for b in bytes(umi):
+        if b in b"-+":
+            continue
+        code = b"ACGT".find(bytes([b]).upper())
+        if code < 0:
+            return 0
+        n += 1
+        if n > UMI_MAX_BASES:
+            return 0
+        bits = (bits << 2) | code
+    return ((1 << (2 * n)) | bits) if n else 0
+
+
+def umi_text(key: int) -> bytes:
+    """The bases a non-zero UMI key stands for (the inverse of umi_pack on a joiner-free upper-case UMI)."""
+    key = int(key)
+    n = (key.bit_length() - 1) // 2
+    return bytes(b"ACGT"[(key >> (2 * (n - 1 - k))) & 3] for k in range(n))

@@ -188,8 +188,8 @@ def write_bam_fast(path, contigs, batch, ch_tag="ch", filter_tag="XF", threads=1
     host_bam_write_ex): used for multi-million-record CLI benchmarks.  Records without names get 16 hex digits of
     their qhash as QNAME (mates keep sharing a name).  seq_mode 0: SEQ all 'A', QUAL 0xff (SURVEY.md 8(d));
     1: random bases and binned Phred-like qualities (the compressibility of a real file).  bai: also write
-    <path>.bai with the per-contig virtual offsets.  Returns the BGZF virtual offsets of the batch's segments
-    (+ the end of the records)."""
+    <path>.bai with the per-contig virtual offsets.  A batch with a umi column gets RX:Z:<bases> behind the other aux fields on
+    every record whose key is not 0.  Returns the BGZF virtual offsets of the batch's segments (+ the end of the records)."""
     import ctypes as C
     import os
     lib = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "librsqc_host.so"))

@@ -23,7 +23,7 @@ inline double now_s() { return std::chrono::duration<double>(std::chrono::steady
 
 void HostBatch::clear() {
     unsorted = false; bad_refid.clear();
-    core.clear(); aux.clear(); qh2.clear(); cigar.clear(); seg_tid.clear(); seg_start.clear();
+    core.clear(); aux.clear(); qh2.clear(); cigar.clear(); umi.clear(); has_umi = false; seg_tid.clear(); seg_start.clear();
     wide_index.clear(); wide_nm.clear(); wide_lq.clear(); wide_ncig.clear();
 }
 
@@ -35,6 +35,7 @@ bool HostBatch::keep_leading_contig(int32_t tid) {
     if (k >= total) return false;
     const size_t c_end = core[k].cigar_off;
     core.resize(k); aux.resize(k); qh2.resize(k); cigar.resize(c_end);
+    if (has_umi) umi.resize(k);
     if (k == 0) { seg_tid.clear(); seg_start.clear(); }
     else { seg_tid.resize(1); seg_start.resize(1); }
     while (!wide_index.empty() && wide_index.back() >= k) { wide_index.pop_back(); wide_nm.pop_back(); wide_lq.pop_back(); wide_ncig.pop_back(); }
@@ -47,6 +48,7 @@ rsqc_batch HostBatch::view() {
     rsqc_batch b{};
     b.n = core.size(); b.file_index_base = file_index_base;
     b.core = core.data(); b.aux = aux.data(); b.qhash2 = qh2.data(); b.cigar = cigar.data(); b.n_cigar_total = cigar.size();
+    b.umi = (has_umi && umi.size() == core.size()) ? umi.data() : nullptr;
     b.n_seg = (uint32_t)seg_tid.size(); b.seg_tid = seg_tid.data(); b.seg_start = seg_start.data();
     b.n_wide = (uint32_t)wide_index.size(); b.wide_index = wide_index.data(); b.wide_nm = wide_nm.data();
     b.wide_l_qseq = wide_lq.data(); b.wide_n_cigar = wide_ncig.data();
@@ -504,6 +506,7 @@ struct ChunkOut {
     std::vector<rsqc_rec_core> core;                     // cigar_off relative to the chunk
     std::vector<rsqc_rec_aux> aux;
     std::vector<uint32_t> qh2;                           // second name hash (rsqc_batch.qhash2)
+    std::vector<uint64_t> umi;                           // UMI keys (rsqc_batch.umi): empty unless the tags select a source
     std::vector<uint32_t> cig;
     std::vector<std::pair<uint32_t, int32_t>> segs;      // (local record index, tid): contig changes inside the chunk (+ its first record)
     std::vector<uint32_t> widx; std::vector<int32_t> wnm, wlq; std::vector<uint32_t> wnc;
@@ -512,7 +515,7 @@ struct ChunkOut {
     // (their names), and positions that go backwards inside a contig (:354); judged on primary, mapped, QC-passed records
     std::vector<std::pair<uint32_t, std::string>> bad_ref;   // (local record index, QNAME)
     bool unsorted = false, have_q = false; int32_t first_tid = 0, first_pos = 0, q_tid = 0, q_pos = 0;
-    void clear() { core.clear(); aux.clear(); qh2.clear(); cig.clear(); cig_end.clear(); segs.clear(); widx.clear(); wnm.clear(); wlq.clear(); wnc.clear(); last_tid = 0;
+    void clear() { core.clear(); aux.clear(); qh2.clear(); umi.clear(); cig.clear(); cig_end.clear(); segs.clear(); widx.clear(); wnm.clear(); wlq.clear(); wnc.clear(); last_tid = 0;
                    bad_ref.clear(); unsorted = false; have_q = false; }
     size_t size() const { return core.size(); }
     // keep the first k records
@@ -520,6 +523,7 @@ struct ChunkOut {
         if (k >= core.size()) return;
         const uint32_t nc = k ? cig_end[k - 1] : 0u;
         core.resize(k); aux.resize(k); qh2.resize(k); cig_end.resize(k); cig.resize(nc);
+        if (!umi.empty()) umi.resize(k);
         while (!segs.empty() && segs.back().first >= k) segs.pop_back();
         while (!widx.empty() && widx.back() >= k) { widx.pop_back(); wnm.pop_back(); wlq.pop_back(); wnc.pop_back(); }
         last_tid = segs.empty() ? 0 : segs.back().second;
@@ -582,6 +586,7 @@ size_t frame_and_parse(const uint8_t *buf, size_t p, size_t limit, size_t end, c
         for (uint32_t ci = 0; ci < ro.n_ops; ++ci) o.cig[c0 + ci] = le32(ops + 4 * (size_t)ci);
         o.cig_end.push_back((uint32_t)o.cig.size());
         o.core.push_back(ro.core); o.aux.push_back(ro.aux); o.qh2.push_back(ro.qhash2);
+        if (tags.umi_src) o.umi.push_back(ro.umi);
         p += 4 + (size_t)block_size;
     }
     o.last_tid = last_tid;
@@ -602,6 +607,7 @@ size_t BamReader::read_batch(HostBatch &out, size_t max_records) {
         tags.f1[tags.n_filter] = filter_tags_[fi].size() == 2 ? filter_tags_[fi][1] : '\0';
         ++tags.n_filter;
     }
+    tags.umi_src = umi_src_; tags.umi_t0 = umi_t0_; tags.umi_t1 = umi_t1_; tags.umi_sep = umi_sep_;
     // diagnostic (tools/decode_sweep.py --inflate-only): consume the inflated stream without framing or parsing it
     static const bool drain_only = getenv("RSQC_HOST_INFLATE_ONLY") != nullptr;
     if (drain_only) { while (fill_group()) pos_ = buf_.size(); return 0; }
@@ -690,6 +696,8 @@ size_t BamReader::read_batch(HostBatch &out, size_t max_records) {
         if (cig_base + cig0[used] > 0x3FFFFFF0ull) throw std::runtime_error("batch too large");
         out.core.resize(base + K); out.aux.resize(base + K); out.qh2.resize(base + K); out.cigar.resize(cig_base + cig0[used]);
         rsqc_rec_core *ocore = out.core.data(); rsqc_rec_aux *oaux = out.aux.data(); uint32_t *oqh2 = out.qh2.data(); uint32_t *ocig = out.cigar.data();
+        uint64_t *oumi = nullptr;
+        if (tags.umi_src) { out.has_umi = true; out.umi.resize(base + K); oumi = out.umi.data(); }
         pool_->run(used, [&](size_t c) {
             const ChunkOut &o = chunks[c];
             const size_t m = o.size();
@@ -699,6 +707,7 @@ size_t BamReader::read_batch(HostBatch &out, size_t max_records) {
             for (size_t k = 0; k < m; ++k) { rsqc_rec_core v = o.core[k]; v.cigar_off += shift; dc[k] = v; }
             memcpy(oaux + base + rec0[c], o.aux.data(), m * sizeof(rsqc_rec_aux));
             memcpy(oqh2 + base + rec0[c], o.qh2.data(), m * sizeof(uint32_t));
+            if (oumi) memcpy(oumi + base + rec0[c], o.umi.data(), m * sizeof(uint64_t));
             if (!o.cig.empty()) memcpy(ocig + cig_base + cig0[c], o.cig.data(), o.cig.size() * sizeof(uint32_t));
         });
         g_t_parse += now_s() - tp;

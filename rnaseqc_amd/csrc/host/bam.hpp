@@ -76,6 +76,8 @@ struct HostBatch {                       // owns the arrays an rsqc_batch points
     RawVec<rsqc_rec_aux> aux;
     RawVec<uint32_t> qh2;                // second name hashes (rsqc_batch.qhash2)
     RawVec<uint32_t> cigar;
+    RawVec<uint64_t> umi;                // UMI keys (rsqc_batch.umi): filled, and handed on by view(), only when the reader has a UMI source
+    bool has_umi = false;
     std::vector<int32_t> seg_tid;
     std::vector<uint64_t> seg_start;
     std::vector<uint64_t> wide_index;
@@ -127,6 +129,8 @@ public:
     const std::vector<uint64_t> &contig_lengths() const { return lengths_; }     // l_ref of the header, in the same order
     // tags: the chimeric tag (2 chars) and up to RSQC_MAX_FILTER_TAGS filter tags
     void set_tags(const std::string &chimeric, const std::vector<std::string> &filters);
+    // --umi-tag / --umi-qname: source (RSQC_UMI_SOURCE_*), the tag's two letters, the name's separator; the batches then carry rsqc_batch.umi
+    void set_umi(int source, char t0, char t1, char sep) { umi_src_ = (uint8_t)source; umi_t0_ = (uint8_t)t0; umi_t1_ = (uint8_t)t1; umi_sep_ = (uint8_t)sep; }
     // appends up to max_records records to `out`; returns the number appended (0 at EOF)
     size_t read_batch(HostBatch &out, size_t max_records);
     uint64_t records_read() const { return n_read_; }
@@ -181,6 +185,7 @@ private:
     std::vector<uint64_t> lengths_;
     std::string ch_tag_ = "ch";
     std::vector<std::string> filter_tags_;
+    uint8_t umi_src_ = 0, umi_t0_ = 0, umi_t1_ = 0, umi_sep_ = 0;
     uint64_t n_read_ = 0;
     bool have_q_ = false; int32_t q_tid_ = 0, q_pos_ = 0;      // last primary mapped record seen (sort check across batches)
 };

@@ -6,6 +6,8 @@
 // seq_mode 0: SEQ all 'A', QUAL 0xff (the contract's BAM).
 // seq_mode 1: random bases and binned Phred-like qualities with runs (the entropy of a real file: inflate costs what it
 //             costs on real data).
+// A batch with the umi column (rsqc_batch.umi) gets an RX:Z aux field behind the others on every record whose key is not 0: the
+// bases the key stands for (the BAM writer only; tools/markdup_umi_bench.py).
 #include <zlib.h>
 
 #include <algorithm>
@@ -132,13 +134,20 @@ HAPI int host_bam_write_ex(const char *path, const char *const *contig_names, co
                 if (b->qname) { name = b->qname + b->qname_off[i]; nlen = b->qname_off[i + 1] - b->qname_off[i]; }
                 else { snprintf(hexname, sizeof hexname, "%016llx", (unsigned long long)au.qhash); name = hexname; nlen = 16; }
                 const int32_t mtid = (au.tagbits & RSQC_TB_MTID_SAME) ? tid : (tid + 1 < n_contigs ? tid + 1 : (tid != 0 ? 0 : -1));
-                uint8_t tags[24]; size_t nt = 0;
+                uint8_t tags[24 + 36]; size_t nt = 0;
                 if (au.tagbits & RSQC_TB_HAS_NM) {
                     tags[nt++] = 'N'; tags[nt++] = 'M';
                     if (nm >= 0 && nm < 256) { tags[nt++] = 'C'; tags[nt++] = (uint8_t)nm; } else { tags[nt++] = 'i'; memcpy(tags + nt, &nm, 4); nt += 4; }
                 }
                 if (au.tagbits & RSQC_TB_HAS_CH) { tags[nt++] = (uint8_t)ch_tag[0]; tags[nt++] = (uint8_t)ch_tag[1]; tags[nt++] = 'Z'; tags[nt++] = '1'; tags[nt++] = 0; }
                 if (au.tagbits & RSQC_TB_FILTER0) { tags[nt++] = (uint8_t)filter_tag[0]; tags[nt++] = (uint8_t)filter_tag[1]; tags[nt++] = 'i'; const uint32_t one = 1; memcpy(tags + nt, &one, 4); nt += 4; }
+                if (b->umi && b->umi[i]) {             // the key's bases: 2 bits each below the length bit (at most 31 of them)
+                    const uint64_t key = b->umi[i];
+                    const int bases = (63 - __builtin_clzll(key)) / 2;
+                    tags[nt++] = 'R'; tags[nt++] = 'X'; tags[nt++] = 'Z';
+                    for (int k = bases - 1; k >= 0; --k) tags[nt++] = (uint8_t)"ACGT"[(key >> (2 * k)) & 3];
+                    tags[nt++] = 0;
+                }
                 const size_t l_seq = lq < 0 ? 0 : (size_t)lq;
                 raw.u32((uint32_t)(32 + nlen + 1 + 4 * (size_t)nc + (l_seq + 1) / 2 + l_seq + nt));
                 raw.u32((uint32_t)tid); raw.u32((uint32_t)co.pos);

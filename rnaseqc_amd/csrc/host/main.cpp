@@ -57,6 +57,9 @@ struct Options {
     bool gene_body = false;            // --gene-body (extension): coverage along the gene body in 100 bins, <sample>.gene_body.tsv (rsqc_genebody_begin / _end / _sums; turns the track on)
     bool junctions = false;            // --junctions (extension): reads per splice junction, <sample>.junctions.tsv (rsqc_junctions_begin / rsqc_junctions_end)
     bool mark_duplicates = false;      // --mark-duplicates (extension, implies --sort): flag 0x400 rewritten on the GPU before the records are counted (rsqc_markdup_begin / rsqc_markdup_end)
+    // --umi-tag=XX / --umi-qname[=C] (extensions, each implies --mark-duplicates): the UMI joins the duplicate signature (rsqc_markdup_use_umi);
+    // the tag's two letters / the separator in front of the UMI at the end of the read name, as given (checked at validation)
+    bool has_umi_tag = false, has_umi_qname = false; std::string umi_tag, umi_sep = "_";
     bool sort = false;                 // --sort (extension): input in any order, put in coordinate order on the GPU (rsqc_sort_begin / rsqc_sort_end)
 };
 
@@ -92,6 +95,8 @@ void usage(std::ostream &o) {
          "      --bam-list=[FILE]                 (extension) A cohort on one GPU: FILE lists one input per line, path[<TAB>sample]; the positionals are [gtf] [output]\n"
          "      --sort                            (extension) Accept input in any order: the records are put in coordinate order on the GPU before they are counted\n"
          "      --mark-duplicates                 (extension) Flag duplicate fragments on the GPU before they are counted: implies --sort, replaces the input's 0x400 flags (one GPU, one input)\n"
+         "      --umi-tag=[XX]                    (extension) UMI-aware --mark-duplicates (implied): the UMI is the Z value of aux tag XX (e.g. RX); exact match, the anchor's UMI, 31 bases at most, N voids it\n"
+         "      --umi-qname=[C]                   (extension) The same with the UMI taken from the read name, behind its last C. Default: _ (use : for bcl-convert names)\n"
          "      --junctions                       (extension) Count reads per splice junction on the GPU and write [sample].junctions.tsv (one GPU)\n"
          "      --bedgraph                        (extension) Build the per-base coverage track on the GPU and write [sample].coverage.bedgraph (one GPU; needs LN in the header)\n"
          "      --gene-body                       (extension) Sum the coverage along every gene's body, 5' to 3' in 100 bins, on the GPU and write [sample].gene_body.tsv (one GPU; needs LN in the header)\n";
@@ -175,6 +180,8 @@ Options parse(int argc, char **argv) {
         else if (name == "bam-list") { o.bam_list = need(); o.has_bam_list = true; }
         else if (name == "sort") o.sort = true;
         else if (name == "mark-duplicates") o.mark_duplicates = o.sort = true;
+        else if (name == "umi-tag") { o.umi_tag = need(); o.has_umi_tag = o.mark_duplicates = o.sort = true; }
+        else if (name == "umi-qname") { if (has_value) o.umi_sep = value; o.has_umi_qname = o.mark_duplicates = o.sort = true; }
         else if (name == "junctions") o.junctions = true;
         else if (name == "bedgraph") o.bedgraph = true;
         else if (name == "gene-body") o.gene_body = true;
@@ -236,6 +243,8 @@ rsqc_decode_params decode_params(const Options &o, int n_ref, uint64_t file_inde
     for (size_t k = 0; k < o.tags.size() && k < RSQC_MAX_FILTER_TAGS; ++k)
         if (o.tags[k].size() == 2) { dp.filter_tag[k][0] = o.tags[k][0]; dp.filter_tag[k][1] = o.tags[k][1]; }   // (other lengths never match)
     dp.file_index_base = file_index_base;
+    if (o.has_umi_tag) { dp.umi_source = RSQC_UMI_SOURCE_TAG; dp.umi_tag[0] = o.umi_tag[0]; dp.umi_tag[1] = o.umi_tag[1]; }      // (lengths checked at validation)
+    if (o.has_umi_qname) { dp.umi_source = RSQC_UMI_SOURCE_QNAME; dp.umi_sep = o.umi_sep[0]; }
     return dp;
 }
 // inflated bytes a call of decode_range can hold: what the device's window buffers are sized for, once (rsqc_decode_begin)
@@ -477,6 +486,8 @@ std::unique_ptr<Input> open_input(const std::string &path, const Options &o) {
         in->reader.reset(new BamReader());
         if (!in->reader->open(reader_path)) { in->error = unable; in->reader.reset(); return in; }
         in->reader->set_tags(o.chimeric_tag, o.tags);
+        if (o.has_umi_tag) in->reader->set_umi(RSQC_UMI_SOURCE_TAG, o.umi_tag[0], o.umi_tag[1], 0);
+        if (o.has_umi_qname) in->reader->set_umi(RSQC_UMI_SOURCE_QNAME, 0, 0, o.umi_sep[0]);
         in->contigs = in->reader->contigs(); in->lengths = in->reader->contig_lengths();
     }
     return in;
@@ -792,6 +803,8 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     if (o.sort && (rc = rsqc_sort_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --mark-duplicates: rsqc_sort_end first rewrites flag 0x400 of the collection
     if (o.mark_duplicates && (rc = rsqc_markdup_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    // --umi-tag / --umi-qname: the UMI key of the decode streams / the host reader's batches joins the signature
+    if ((o.has_umi_tag || o.has_umi_qname) && (rc = rsqc_markdup_use_umi(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --junctions: every batch the per-read kernels run leaves its junction instances on the device (under --sort: the sorted batches)
     if (o.junctions && (rc = rsqc_junctions_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --bedgraph: and its coverage events, in a difference array over the header's contigs (kept by the context while it is large enough)
@@ -899,6 +912,10 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
             cout << "Duplicates marked: records " << md.records << ", population " << md.population << ", anchors " << md.anchors << ", sets " << md.sets
                  << ", duplicate_fragments " << md.duplicate_fragments << ", flagged_records " << md.flagged_records << ", cleared_records " << md.cleared_records
                  << ", sig_ms " << md.sig_ms << ", sort_ms " << md.sort_ms << ", mark_ms " << md.mark_ms << endl;
+        rsqc_markdup_umi_info mu{};
+        if ((o.has_umi_tag || o.has_umi_qname) && rc == RSQC_OK && (rc = rsqc_markdup_umi_end(gpu, &mu)) == RSQC_OK && o.verbosity)
+            cout << "UMIs in the signature: anchors_with_umi " << mu.anchors_with_umi << ", anchors_without_umi " << mu.anchors_without_umi
+                 << ", position_duplicate_fragments " << mu.position_duplicate_fragments << endl;
     }
     rsqc_results res{};
     if (rc == RSQC_OK) rc = rsqc_finalize(gpu, &res);
@@ -1248,6 +1265,9 @@ int main(int argc, char **argv) {
             else if (o.stranded == "FR" || o.stranded == "fr") strand = RSQC_STRAND_FORWARD;
             else throw ValidationError("--stranded argument must be in {'RF', 'rf', 'FR', 'fr'}");
         }
+        if (o.has_umi_tag && o.has_umi_qname) throw ValidationError("--umi-tag and --umi-qname name two sources of the UMI: give one");
+        if (o.has_umi_tag && o.umi_tag.size() != 2) throw ValidationError("--umi-tag takes the two characters of an aux tag (e.g. RX)");
+        if (o.has_umi_qname && o.umi_sep.size() != 1) throw ValidationError("--umi-qname takes one separator character (default _)");
         if (o.mark_duplicates) {
             // the whole input must be resident: the stage runs on the collection of --sort, in ONE context
             if (o.has_bam_list) throw ValidationError("--mark-duplicates takes one input (it cannot be combined with --bam-list)");

@@ -109,7 +109,7 @@ void rsqc_destroy(rsqc_ctx *c) {
     {
         DecodeState &D = c->dec;
         for (DevBuf *b : {&D.comp, &D.blocks, &D.ubuf, &D.seg, &D.seg_rec0, &D.seg_ops0, &D.rec_off, &D.ops_at, &D.mark, &D.core, &D.aux, &D.qh2, &D.cigar,
-                          &D.seg_tid, &D.seg_start, &D.wide_index, &D.wide_nm, &D.wide_lq, &D.wide_nc, &D.sum, &D.carry, &D.tailtmp, &D.scratch}) b->release();
+                          &D.seg_tid, &D.seg_start, &D.wide_index, &D.wide_nm, &D.wide_lq, &D.wide_nc, &D.sum, &D.carry, &D.tailtmp, &D.scratch, &D.umi}) b->release();
         if (D.h_sum) (void)hipHostFree(D.h_sum);
         if (D.h_blocks) (void)hipHostFree(D.h_blocks);
         if (D.ev_copy) (void)hipEventDestroy(D.ev_copy);
@@ -480,3 +480,4 @@ uint64_t rsqc_qname_hash(const char *name, size_t len) {
 }
 
 uint32_t rsqc_qname_hash2(const char *name, size_t len) { return rsqc::bam_qname_hash2((const uint8_t *)name, (uint32_t)len); }
+uint64_t rsqc_umi_pack(const char *umi, uint32_t len) { return umi ? rsqc::umi_pack((const uint8_t *)umi, len) : 0ull; }

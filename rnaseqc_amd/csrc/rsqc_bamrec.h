@@ -11,6 +11,7 @@
 
 #include <stdint.h>
 #include "../../include/rnaseqc_amd.h"
+#include "rsqc_umi.h"
 
 #if defined(__HIPCC__)
 #define RSQC_BAM_FN __host__ __device__ __forceinline__
@@ -50,6 +51,8 @@ struct BamTagSpec {
     int32_t n_ref;
     uint8_t have_ch, ch0, ch1, n_filter;
     uint8_t f0[RSQC_MAX_FILTER_TAGS], f1[RSQC_MAX_FILTER_TAGS];
+    // --umi-tag / --umi-qname (rsqc_umi.h): RSQC_UMI_NONE / _TAG / _QNAME, the tag's two letters, the name's separator byte
+    uint8_t umi_src, umi_t0, umi_t1, umi_sep;
 };
 
 // structural check used to GUESS a record start inside inflated data (a guess is always verified by the true chain)
@@ -138,6 +141,7 @@ struct BamRecOut {
     uint32_t wide;
     uint32_t qname_len;          // bytes before the NUL
     uint32_t qhash2;             // rsqc_qname_hash2 of the name (the batch's qhash2 column)
+    uint64_t umi;                // the record's UMI key (rsqc_umi.h; the batch's umi column): 0 without a source or a usable UMI
 };
 
 // one record; false = malformed ("bad BAM record")
@@ -176,12 +180,14 @@ RSQC_BAM_FN bool bam_parse_record(const uint8_t *rec, uint32_t block_size, const
     }
     o.qname_len = qlen;
     o.qhash2 = bam_qh2_finish(qh2, qlen);
+    o.umi = tags.umi_src == RSQC_UMI_QNAME ? umi_from_qname(r + 32, qlen, tags.umi_sep) : 0ull;     // (a backward scan of its own: the loop above stays as it is)
     o.core.pos = pos; o.core.mpos = mpos; o.core.isize = isize; o.core.cigar_off = 0;
     o.aux.qhash = qh;
     o.aux.flag = (uint16_t)flag; o.aux.mapq = (uint8_t)mapq;
     o.tid = tid;
     uint32_t tagbits = (tid == mtid) ? RSQC_TB_MTID_SAME : 0;
     int32_t nm = 0;
+    bool umi_open = tags.umi_src == RSQC_UMI_TAG;                                   // the first field of that name counts
     const uint64_t aux_at = 32ull + l_name + 4ull * n_cigar + (uint64_t)((l_seq < 0 ? 0 : l_seq + 1) / 2) + (uint64_t)(l_seq < 0 ? 0 : l_seq);
     if (aux_at <= block_size) {
         for (const uint8_t *q = r + aux_at; q + 3 <= end_r;) {
@@ -198,6 +204,10 @@ RSQC_BAM_FN bool bam_parse_record(const uint8_t *rec, uint32_t block_size, const
                     int32_t x;
                     if (type == 'Z' || type == 'f' || bam_aux_int(v, type, x)) tagbits |= (uint32_t)RSQC_TB_FILTER0 << fi;
                 }
+            if (umi_open && t0 == (char)tags.umi_t0 && t1 == (char)tags.umi_t1) {   // a Z value: vlen - 1 bytes and their NUL, inside the record
+                umi_open = false;
+                if (type == 'Z') o.umi = umi_pack(v, vlen - 1u);
+            }
             q = v + vlen;
         }
     }

@@ -47,6 +47,7 @@ struct UploadedBatch {
     std::vector<uint64_t> seg_file_index, seg_records;   // a batch of several file ranges (rsqc_batch.seg_file_index): per segment
     DevBuf rl_seg;                                   // ... and its per-segment Read-Length inputs [3 * n_seg] (armed at every submit)
     bool pooled = false;           // transient upload: its buffers go back to the context's pool
+    const uint64_t *umi = nullptr; // rsqc_batch.umi on the device (a pass under rsqc_markdup_use_umi only): read by the collection, by no kernel of the batch
 };
 
 // What a submitted batch leaves behind for the end-of-file stage is written into WORST-CASE sized buffers (the counts
@@ -96,6 +97,7 @@ struct DecodeState {
     size_t out_cap = 0, comp_cap = 0, blk_cap = 0;
     DevBuf comp, blocks, ubuf, seg, seg_rec0, seg_ops0, rec_off, ops_at, mark, core, aux, qh2, cigar, seg_tid, seg_start,
            wide_index, wide_nm, wide_lq, wide_nc, sum, carry, tailtmp, scratch;
+    DevBuf umi;                        // the window's UMI keys: allocated only when tags.umi_src selects a source
     DecodeSummary *h_sum = nullptr;    // page-locked
     DevBgzfBlock *h_blocks = nullptr;  // page-locked, blk_cap entries
     bool unsorted = false;
@@ -133,6 +135,7 @@ struct SortState {
     bool active = false;
     uint64_t n = 0, n_ops = 0, n_wide = 0, cap_n = 0, cap_ops = 0, cap_wide = 0, batches_in = 0;
     DevBuf core, aux, qh2, key, cigar, wide_index, wide_nm, wide_lq, wide_nc;
+    DevBuf umi; uint64_t cap_umi = 0;                // rsqc_markdup_use_umi only: the records' UMI keys, 8 bytes each, released by the marking stage
     std::vector<uint64_t> batch_rec0, batch_pool0;   // first record / first operation of every collected batch
 };
 
@@ -155,6 +158,9 @@ struct MarkdupState {
     uint64_t n = 0;                                    // records of the collection the verdicts are for
     int passes_lo = 0, passes_hi = 0;                  // live radix passes of the two sort stages
     rsqc_markdup_info info{};
+    bool use_umi = false;                              // rsqc_markdup_use_umi: the UMI key is part of the signature
+    int passes_mapq = 0, passes_umi = 0;               // ... and the live passes of its two extra sort stages
+    rsqc_markdup_umi_info umi_info{};
     DevBuf verdict;
     std::vector<uint8_t> h_verdict;                    // the window of the last rsqc_markdup_verdicts
 };

@@ -48,6 +48,7 @@ struct DecodeWindow {
     uint64_t *wide_index; int32_t *wide_nm, *wide_lq; uint32_t *wide_nc;
     DecodeSummary *sum; DecodeCarry *carry;
     BamTagSpec tags;
+    uint64_t *umi;                                         // the UMI keys (rsqc_batch.umi): null unless tags.umi_src selects a source
 };
 
 RSQC_BAM_FN void decode_segment_bounds(const DecodeWindow &W, uint32_t s, uint32_t &lo, uint32_t &hi) {
@@ -78,6 +79,7 @@ RSQC_BAM_FN uint32_t decode_parse_one(const DecodeWindow &W, uint32_t i, bool &u
     const uint32_t at = W.ops_at[i];
     ro.core.cigar_off = at;
     W.core[i] = ro.core; W.aux[i] = ro.aux; W.qh2[i] = ro.qhash2;
+    if (W.umi) W.umi[i] = ro.umi;
     const uint8_t *ops = rec + ro.ops_off;
     for (uint32_t k = 0; k < ro.n_ops; ++k) W.cigar[at + k] = bam_ld32(ops + 4u * k);
     uint32_t m = 0;

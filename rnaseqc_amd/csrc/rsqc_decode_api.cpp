@@ -55,6 +55,11 @@ int decode_reserve(rsqc_ctx *c, size_t out_bytes, size_t comp_bytes, size_t n_bl
     D.ubuf.release(); D.ubuf = nu;
     return reserve_columns(c, W, cap);
 }
+// the UMI column of a window, only for a stream with a UMI source: as many entries as the qh2 column has (twice its bytes)
+int reserve_umi(rsqc_ctx *c) {
+    DecodeState &D = c->dec;
+    return D.tags.umi_src ? dev_alloc(c, D.umi, D.qh2.bytes * 2, false) : 0;
+}
 // a SAM window the device stages refused: the first malformed line, found again on the host with the same functions, and its
 // line number in the stream (rare path: the window's text is copied back)
 void sam_window_error(rsqc_ctx *c, const DecodeWindow &W, std::string &msg) {
@@ -130,12 +135,13 @@ int decode_finish(rsqc_ctx *c, rsqc_decode_window *out) {
     if (out) { out->n_records = S.n_rec; out->n_runs = S.n_seg; out->run_tid = D.run_tid.data(); out->device_batch = rsqc_batch{}; }
     if (S.n_rec) {
         window_columns(D.last, W, S);
-        D.last.file_index_base = D.next_file_index; D.last.n_cigar_total = S.n_ops;
+        D.last.file_index_base = D.next_file_index; D.last.n_cigar_total = S.n_ops; D.last.umi = W.umi;
         if (out && !D.pipelined) out->device_batch = D.last;     // (pipelined: the next call's kernels are already queued into these buffers)
         UploadedBatch *u = new UploadedBatch();
         u->pooled = false;
         u->n = S.n_rec; u->n_cigar_total = S.n_ops; u->file_index_base = D.next_file_index;
         window_columns(u->d, W, S);
+        u->umi = W.umi;
         c->transient.push_back(u);
         D.next_file_index += S.n_rec; D.records += S.n_rec;
         if ((rc = run_batch(c, u))) return rc;
@@ -166,6 +172,7 @@ void window_buffers(DecodeWindow &W, const DecodeState &D) {
     W.seg_tid = (int32_t *)D.seg_tid.p; W.seg_start = (uint64_t *)D.seg_start.p;
     W.wide_index = (uint64_t *)D.wide_index.p; W.wide_nm = (int32_t *)D.wide_nm.p; W.wide_lq = (int32_t *)D.wide_lq.p; W.wide_nc = (uint32_t *)D.wide_nc.p;
     W.sum = (DecodeSummary *)D.sum.p; W.carry = (DecodeCarry *)D.carry.p; W.tags = D.tags;
+    W.umi = D.tags.umi_src ? (uint64_t *)D.umi.p : nullptr;
 }
 void sam_window_buffers(SamWindow &S, const DecodeState &D, const DecodeWindow &W) {
     S.W = W;
@@ -194,7 +201,7 @@ int decode_enqueue(rsqc_ctx *c, const void *compressed, uint64_t compressed_byte
         // (finishing the call in flight may have enlarged the head room for a carried-over record: the limit is about THIS origin)
         if ((rc = check_window_limit(c, total))) return rc;
     }
-    if ((rc = decode_reserve(c, (size_t)total, (size_t)compressed_bytes, n_blocks))) return rc;
+    if ((rc = decode_reserve(c, (size_t)total, (size_t)compressed_bytes, n_blocks)) || (rc = reserve_umi(c))) return rc;
     DevBgzfBlock *hb = D.h_blocks + (size_t)slot * D.blk_cap;
     uint32_t raw_at = D.head;                                           // where the caller-inflated run goes in the window
     uint32_t head_used = D.head;                                        // the window origin the table below was laid out for
@@ -220,7 +227,7 @@ int decode_enqueue(rsqc_ctx *c, const void *compressed, uint64_t compressed_byte
         // (inflating to the old places would overwrite the carried bytes and shift the window)
         if ((rc = check_window_limit(c, total))) { (void)hipStreamSynchronize(D.copy_stream); return rc; }
         HIP_TRY(c, hipStreamSynchronize(D.copy_stream));               // (the first copy of the table reads hb)
-        if ((rc = decode_reserve(c, (size_t)total, (size_t)compressed_bytes, n_blocks))) return rc;
+        if ((rc = decode_reserve(c, (size_t)total, (size_t)compressed_bytes, n_blocks)) || (rc = reserve_umi(c))) return rc;
         lay_out_blocks();
         if (n_gpu) HIP_TRY(c, hipMemcpyAsync(dblk, hb, (size_t)n_gpu * sizeof(DevBgzfBlock), hipMemcpyHostToDevice, D.copy_stream));
         HIP_TRY(c, hipEventRecord(D.ev_copy, D.copy_stream));
@@ -280,6 +287,8 @@ int decode_begin_common(rsqc_ctx *c, const rsqc_decode_params *p, bool sam) {
     if (p->has_chimeric_tag) { D.tags.have_ch = 1; D.tags.ch0 = (uint8_t)p->chimeric_tag[0]; D.tags.ch1 = (uint8_t)p->chimeric_tag[1]; }
     D.tags.n_filter = (uint8_t)c->params.n_filter_tags;
     for (int k = 0; k < c->params.n_filter_tags; ++k) { D.tags.f0[k] = (uint8_t)p->filter_tag[k][0]; D.tags.f1[k] = (uint8_t)p->filter_tag[k][1]; }
+    if (p->umi_source > RSQC_UMI_SOURCE_QNAME) return fail(c, RSQC_ERR_ARG, "rsqc_decode_params.umi_source: 0 (none), 1 (tag) or 2 (read name)");
+    D.tags.umi_src = p->umi_source; D.tags.umi_t0 = (uint8_t)p->umi_tag[0]; D.tags.umi_t1 = (uint8_t)p->umi_tag[1]; D.tags.umi_sep = (uint8_t)p->umi_sep;
     D.next_file_index = p->file_index_base; D.records = 0; D.tail = 0;
     D.unsorted = false; D.n_bad = 0; D.bad_names.clear();
     D.pipelined = p->pipelined != 0; D.pending = false; D.slot = 0;

@@ -19,6 +19,16 @@
 //   markdup_apply_kernel       per record: probe until an equal name or an empty slot, rewrite the flag of its OWN record (a 16-bit
 //                              store: other lanes read the qhash beside it), the verdict byte, and two counters -- a ballot and a
 //                              popcount per wave, then one atomic per wave and counter
+//
+// rsqc_markdup_use_umi (--umi-tag / --umi-qname): the anchor's UMI key (rsqc_umi.h) is the LAST component of the signature.  Two more
+// kernels, every kernel above unchanged:
+//   markdup_umi_keys_kernel    per anchor slot its record's key from the collection's umi column (through ci), and how many are not 0
+//   (the order becomes (K_hi, K_lo >> 8, umi, 255 - mapq, arrival): LSD in FOUR stages of the same radix pass -- the mapq byte of K_lo,
+//    the live digits of the UMI keys, K_lo above its mapq byte, K_hi -- each stage's keys gathered through the payload of the stage
+//    before with markdup_permute_kernel; a stage without a live digit is skipped with its gather.  The UMI has to rank ABOVE the mapq
+//    byte: below it, anchors of one signature and UMI but different mapq would not be adjacent)
+//   markdup_heads_umi_kernel   1 where signature AND key are the predecessor's; beside it the number of anchors whose signature alone
+//                              is the predecessor's -- what the marking without the UMI would have called (position_duplicate_fragments)
 #pragma once
 
 #if !defined(RSQC_WAVE_EMU)
@@ -45,6 +55,7 @@ struct MarkdupCollection {
     const uint64_t *batch_rec0, *batch_pool0; uint32_t n_batches;      // first record / first operation of input batch k
     const uint64_t *wide_index; const uint32_t *wide_n_cigar; uint64_t n_wide;
     uint64_t n_ops;                                                    // operations in `cigar`: no record reads past them
+    const uint64_t *umi;                                               // rsqc_markdup_use_umi: the records' UMI keys; null otherwise (no kernel above the _umi ones reads it)
 };
 
 // the size of the name table for n_dup duplicate anchors: a power of two, at least twice their number and at least 1024
@@ -184,6 +195,39 @@ __global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_list_kernel(const uin
     if (through != before && (uint64_t)before < total[0] && s < n) dup_list[before] = ci[s];
 }
 
+// ---- rsqc_markdup_use_umi: the UMI key is the LAST component of the signature ----------------------------------------------------
+// stage 2b: the anchors' own keys by slot, gathered through ci; counters[3] += anchors whose key is not 0
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_umi_keys_kernel(MarkdupCollection C, const uint32_t *ci, uint64_t n_anchors, uint64_t *k_umi, unsigned long long *counters) {
+    const uint64_t a = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    uint64_t u = 0;
+    if (a < n_anchors) {
+        const uint64_t i = ci[a];
+        if (C.umi && i < C.n) u = C.umi[i];
+        k_umi[a] = u;
+    }
+    uint32_t with = 0;                                 // (one atomic per workgroup: nearly every wave has such an anchor, and they all add to ONE word)
+    (void)md_block_scan(u != 0 ? 1u : 0u, with);
+    if (threadIdx.x == 0 && with) atomicAdd(&counters[3], (unsigned long long)with);
+}
+// stage 4 in this mode.  The order is (K_hi, K_lo >> 8, umi, 255 - mapq, arrival): anchors of one position signature are adjacent, and
+// inside them the anchors of one UMI.  mark = 1 where signature AND UMI are the predecessor's; counters[4] += anchors whose position
+// signature alone is the predecessor's -- the duplicate fragments of a marking without the UMI
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_heads_umi_kernel(const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, const uint64_t *k_umi, uint64_t n, uint32_t *mark,
+                                                                             unsigned long long *counters) {
+    const uint64_t r = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    bool pos_dup = false, dup = false;
+    if (r < n) {
+        if (r > 0 && key[r] == key[r - 1]) {
+            const uint32_t s = idx[r], p = idx[r - 1];
+            if (s < n && p < n && (k_lo[s] >> 8) == (k_lo[p] >> 8)) { pos_dup = true; dup = k_umi[s] == k_umi[p]; }
+        }
+        mark[r] = dup ? 1u : 0u;
+    }
+    uint32_t pm = 0;
+    (void)md_block_scan(pos_dup ? 1u : 0u, pm);
+    if (threadIdx.x == 0 && pm) atomicAdd(&counters[4], (unsigned long long)pm);
+}
+
 // ---- stage 5: the names of the duplicate anchors; table: mask + 1 slots, all RSQC_MD_EMPTY --------------------------------------
 __global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_insert_kernel(MarkdupCollection C, const uint32_t *dup_list, uint64_t n_dup, uint32_t *table, uint32_t mask) {
     const uint64_t j = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
@@ -237,6 +281,8 @@ void launch_markdup_signature(hipStream_t s, const MarkdupCollection &C, const u
 void launch_markdup_permute(hipStream_t s, const uint64_t *k_hi, const uint32_t *idx, uint64_t n, uint64_t *key);
 void launch_markdup_heads(hipStream_t s, const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, uint64_t n, uint32_t *mark);
 void launch_markdup_list(hipStream_t s, const uint32_t *at, const unsigned long long *total, const uint32_t *idx, const uint32_t *ci, uint64_t n, uint32_t *dup_list);
+void launch_markdup_umi_keys(hipStream_t s, const MarkdupCollection &C, const uint32_t *ci, uint64_t n_anchors, uint64_t *k_umi, unsigned long long *counters);
+void launch_markdup_heads_umi(hipStream_t s, const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, const uint64_t *k_umi, uint64_t n, uint32_t *mark, unsigned long long *counters);
 void launch_markdup_insert(hipStream_t s, const MarkdupCollection &C, const uint32_t *dup_list, uint64_t n_dup, uint32_t *table, uint32_t mask);
 void launch_markdup_apply(hipStream_t s, const MarkdupCollection &C, const uint32_t *dup_list, uint64_t n_dup, const uint32_t *table, uint32_t mask, uint8_t *verdict, unsigned long long *counters);
 #endif

@@ -31,6 +31,16 @@ void launch_markdup_list(hipStream_t s, const uint32_t *at, const unsigned long 
     markdup_list_kernel<<<blocks_for(n, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(at, total, idx, ci, n, dup_list);
 }
 
+void launch_markdup_umi_keys(hipStream_t s, const MarkdupCollection &C, const uint32_t *ci, uint64_t n_anchors, uint64_t *k_umi, unsigned long long *counters) {
+    if (!n_anchors) return;
+    markdup_umi_keys_kernel<<<blocks_for(n_anchors, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(C, ci, n_anchors, k_umi, counters);
+}
+
+void launch_markdup_heads_umi(hipStream_t s, const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, const uint64_t *k_umi, uint64_t n, uint32_t *mark, unsigned long long *counters) {
+    if (!n) return;
+    markdup_heads_umi_kernel<<<blocks_for(n, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(key, idx, k_lo, k_umi, n, mark, counters);
+}
+
 void launch_markdup_insert(hipStream_t s, const MarkdupCollection &C, const uint32_t *dup_list, uint64_t n_dup, uint32_t *table, uint32_t mask) {
     if (!n_dup) return;
     markdup_insert_kernel<<<blocks_for(n_dup, RSQC_MD_THREADS), RSQC_MD_THREADS, 0, s>>>(C, dup_list, n_dup, table, mask);

@@ -27,8 +27,9 @@ int alloc_or_capacity(rsqc_ctx *c, DevBuf &b, size_t bytes, const char *what, ui
 // scratch of the stage: released before markdup_run returns, so before the coordinate sort allocates
 struct Scratch {
     DevBuf batch_tab, block_anchors, counters, totals, chunk_sum, k_hi, k_lo, ci, key0, key1, idx0, idx1, hist, part, table;
-    size_t bytes() { size_t n = 0; for (DevBuf *b : {&batch_tab, &block_anchors, &counters, &totals, &chunk_sum, &k_hi, &k_lo, &ci, &key0, &key1, &idx0, &idx1, &hist, &part, &table}) n += b->bytes; return n; }
-    void release() { for (DevBuf *b : {&batch_tab, &block_anchors, &counters, &totals, &chunk_sum, &k_hi, &k_lo, &ci, &key0, &key1, &idx0, &idx1, &hist, &part, &table}) b->release(); }
+    DevBuf k_umi;                                      // rsqc_markdup_use_umi only: the anchors' UMI keys by slot
+    size_t bytes() { size_t n = 0; for (DevBuf *b : {&batch_tab, &block_anchors, &counters, &totals, &chunk_sum, &k_hi, &k_lo, &ci, &key0, &key1, &idx0, &idx1, &hist, &part, &table, &k_umi}) n += b->bytes; return n; }
+    void release() { for (DevBuf *b : {&batch_tab, &block_anchors, &counters, &totals, &chunk_sum, &k_hi, &k_lo, &ci, &key0, &key1, &idx0, &idx1, &hist, &part, &table, &k_umi}) b->release(); }
 };
 
 int markdup_stage(rsqc_ctx *c, Scratch &X) {
@@ -54,6 +55,7 @@ int markdup_stage(rsqc_ctx *c, Scratch &X) {
     C.key = (const uint64_t *)S.key.p; C.cigar = (const uint32_t *)S.cigar.p; C.n = N;
     C.batch_rec0 = (const uint64_t *)X.batch_tab.p; C.batch_pool0 = C.batch_rec0 + nb + 1; C.n_batches = (uint32_t)nb;
     C.wide_index = (const uint64_t *)S.wide_index.p; C.wide_n_cigar = (const uint32_t *)S.wide_nc.p; C.n_wide = S.n_wide; C.n_ops = S.n_ops;
+    C.umi = M.use_umi ? (const uint64_t *)S.umi.p : nullptr;
     unsigned long long *d_cnt = (unsigned long long *)X.counters.p, *d_tot = (unsigned long long *)X.totals.p, *d_chunk = (unsigned long long *)X.chunk_sum.p;
     // ---- 1 mark, 2 signature (host clocks around kernels and the synchronisation behind them; allocations are outside them)
     auto t0 = std::chrono::steady_clock::now();
@@ -77,7 +79,8 @@ int markdup_stage(rsqc_ctx *c, Scratch &X) {
             (rc = alloc_or_capacity(c, X.ci, A * 4 + 64, "the anchors' record indices", A)) || (rc = alloc_or_capacity(c, X.key0, A * 8 + 64, "the sort's key column", A)) ||
             (rc = alloc_or_capacity(c, X.key1, A * 8 + 64, "the sort's second key column", A)) || (rc = alloc_or_capacity(c, X.idx0, A * 4 + 64, "the sort's index column", A)) ||
             (rc = alloc_or_capacity(c, X.idx1, A * 4 + 64, "the sort's second index column", A)) || (rc = alloc_or_capacity(c, X.hist, 256 * tiles * 4 + 64, "the digit histograms", A)) ||
-            (rc = alloc_or_capacity(c, X.chunk_sum, scan_chunks * 8, "the scan's chunk sums", A)) || (rc = alloc_or_capacity(c, X.part, (size_t)prep_grid * 48, "the key reduction", A))) return rc;
+            (rc = alloc_or_capacity(c, X.chunk_sum, scan_chunks * 8, "the scan's chunk sums", A)) || (rc = alloc_or_capacity(c, X.part, (size_t)prep_grid * (M.use_umi ? 72 : 48), "the key reduction", A)) ||
+            (M.use_umi && (rc = alloc_or_capacity(c, X.k_umi, A * 8 + 64, "the UMI key column", A)))) return rc;
         d_chunk = (unsigned long long *)X.chunk_sum.p;
         uint64_t *kbuf[2] = {(uint64_t *)X.key0.p, (uint64_t *)X.key1.p};
         uint32_t *ibuf[2] = {(uint32_t *)X.idx0.p, (uint32_t *)X.idx1.p};
@@ -85,23 +88,46 @@ int markdup_stage(rsqc_ctx *c, Scratch &X) {
         unsigned long long *d_part = (unsigned long long *)X.part.p;
         t0 = std::chrono::steady_clock::now();
         launch_markdup_signature(c->stream, C, (const uint32_t *)X.block_anchors.p, A, (uint64_t *)X.k_hi.p, (uint64_t *)X.k_lo.p, kbuf[0], (uint32_t *)X.ci.p);
+        if (M.use_umi) launch_markdup_umi_keys(c->stream, C, (const uint32_t *)X.ci.p, A, (uint64_t *)X.k_umi.p, d_cnt);
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
         info.sig_ms += ms_since(t0);
         // ---- 3 sort: LSD over (K_hi, K_lo) in two stages of 64-bit radix passes, dead digit positions skipped in both.  OR and AND
         // of both parts in one read-back; the index column the second prepare call writes is scratch
         t0 = std::chrono::steady_clock::now();
+        const uint64_t *k_umi = (const uint64_t *)X.k_umi.p;
+        const int n_parts = M.use_umi ? 3 : 2;         // K_lo, K_hi and, in the UMI mode, the UMI keys
+        if (M.use_umi) launch_sort_prepare(c->stream, k_umi, A, ibuf[1], d_part + (size_t)prep_grid * 6, prep_grid);
         launch_sort_prepare(c->stream, k_hi, A, ibuf[1], d_part + (size_t)prep_grid * 3, prep_grid);
         launch_sort_prepare(c->stream, kbuf[0], A, ibuf[0], d_part, prep_grid);
-        std::vector<unsigned long long> part((size_t)prep_grid * 6);
+        std::vector<unsigned long long> part((size_t)prep_grid * 3 * (size_t)n_parts);
         HIP_TRY(c, hipMemcpyAsync(part.data(), X.part.p, part.size() * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
-        uint64_t oa[2][2] = {{0, ~0ull}, {0, ~0ull}};
-        for (int h = 0; h < 2; ++h)
+        uint64_t oa[3][2] = {{0, ~0ull}, {0, ~0ull}, {0, ~0ull}};
+        for (int h = 0; h < n_parts; ++h)
             for (uint32_t k = 0; k < prep_grid; ++k) { oa[h][0] |= part[(size_t)h * prep_grid * 3 + 3 * k]; oa[h][1] &= part[(size_t)h * prep_grid * 3 + 3 * k + 1]; }
         int shift[8], kc = 0, ic = 0;                  // kbuf[kc] / ibuf[ic]: the current keys and payload
-        const int n_lo = sort_live_digits(oa[0][0], oa[0][1], shift);
+        auto passes = [&](int n, const int *sh) {
+            for (int p = 0; p < n; ++p) {
+                launch_sort_pass(c->stream, kbuf[kc], ibuf[ic], kbuf[kc ^ 1], ibuf[ic ^ 1], A, sh[p], (uint32_t *)X.hist.p, d_chunk, d_tot);
+                kc ^= 1; ic ^= 1;
+            }
+        };
+        int n_lo = sort_live_digits(oa[0][0], oa[0][1], shift);
+        if (M.use_umi) {
+            // the UMI ranks ABOVE the mapq byte: (K_hi, K_lo >> 8, umi, 255 - mapq, arrival).  LSD: the mapq byte alone, then the UMI keys, then
+            // K_lo above its lowest byte -- each stage's keys gathered through the payload of the stage before, a stage without a live digit
+            // skipped with its gather; K_hi follows below as ever
+            const int n_mapq = (n_lo && shift[0] == 0) ? 1 : 0;
+            passes(n_mapq, shift);
+            int shift_u[8];
+            const int n_umi = sort_live_digits(oa[2][0], oa[2][1], shift_u);
+            if (n_umi) { launch_markdup_permute(c->stream, k_umi, ibuf[ic], A, kbuf[kc]); passes(n_umi, shift_u); }
+            if (n_lo - n_mapq) { launch_markdup_permute(c->stream, k_lo, ibuf[ic], A, kbuf[kc]); passes(n_lo - n_mapq, shift + n_mapq); }
+            M.passes_mapq = n_mapq; M.passes_umi = n_umi;
+            n_lo -= n_mapq;
+        } else
         for (int p = 0; p < n_lo; ++p) {               // stage 1: by K_lo
             launch_sort_pass(c->stream, kbuf[kc], ibuf[ic], kbuf[kc ^ 1], ibuf[ic ^ 1], A, shift[p], (uint32_t *)X.hist.p, d_chunk, d_tot);
             kc ^= 1; ic ^= 1;
@@ -120,7 +146,8 @@ int markdup_stage(rsqc_ctx *c, Scratch &X) {
         // ---- 4 heads: the marks take the payload's free buffer, D the keys' free buffer
         t0 = std::chrono::steady_clock::now();
         uint32_t *mark = ibuf[ic ^ 1], *list = (uint32_t *)kbuf[kc ^ 1];
-        launch_markdup_heads(c->stream, kbuf[kc], ibuf[ic], k_lo, A, mark);
+        if (M.use_umi) launch_markdup_heads_umi(c->stream, kbuf[kc], ibuf[ic], k_lo, k_umi, A, mark, d_cnt);
+        else launch_markdup_heads(c->stream, kbuf[kc], ibuf[ic], k_lo, A, mark);
         launch_sort_scan(c->stream, mark, A, d_chunk, d_tot);
         launch_markdup_list(c->stream, mark, d_tot, ibuf[ic], (const uint32_t *)X.ci.p, A, list);
         HIP_TRY(c, hipMemcpyAsync(&n_dup, d_tot, 8, hipMemcpyDeviceToHost, c->stream));
@@ -145,17 +172,22 @@ int markdup_stage(rsqc_ctx *c, Scratch &X) {
         launch_markdup_insert(c->stream, C, d_list, n_dup, (uint32_t *)X.table.p, mask);
     }
     launch_markdup_apply(c->stream, C, d_list, n_dup, n_dup ? (const uint32_t *)X.table.p : nullptr, mask, (uint8_t *)M.verdict.p, d_cnt);
-    unsigned long long cnt[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, 24, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long cnt[5] = {0, 0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, 40, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     info.mark_ms += ms_since(t0);
     info.flagged_records = cnt[1]; info.cleared_records = cnt[2];
+    if (M.use_umi) {
+        if (cnt[3] > A || cnt[4] >= std::max<unsigned long long>(A, 1) || cnt[4] < n_dup) return fail(c, RSQC_ERR_HIP, "rsqc_sort_end: the UMI figures of the duplicate marking do not add up");
+        M.umi_info.anchors_with_umi = cnt[3]; M.umi_info.anchors_without_umi = A - cnt[3]; M.umi_info.position_duplicate_fragments = cnt[4];
+    }
     // RSQC_MARKDUP_PROFILE: what the sort stages had to move (tools/markdup_bench.py) -- key + payload, read and written once per pass
     // and what the stage holds on the device at its end, the verdict column included (nothing is freed before)
     if (getenv("RSQC_MARKDUP_PROFILE"))
-        fprintf(stderr, "markdup: anchors %llu, passes_lo %d, passes_hi %d, radix_bytes %llu, table_slots %llu, device_bytes %llu\n", A, M.passes_lo, M.passes_hi,
-                (unsigned long long)(M.passes_lo + M.passes_hi) * 2ull * 12ull * A, n_dup ? (unsigned long long)mask + 1ull : 0ull, (unsigned long long)(X.bytes() + M.verdict.bytes));
+        fprintf(stderr, "markdup: anchors %llu, passes_lo %d, passes_hi %d, radix_bytes %llu, table_slots %llu, device_bytes %llu%s\n", A, M.passes_lo, M.passes_hi,
+                (unsigned long long)(M.passes_lo + M.passes_hi + M.passes_mapq + M.passes_umi) * 2ull * 12ull * A, n_dup ? (unsigned long long)mask + 1ull : 0ull, (unsigned long long)(X.bytes() + M.verdict.bytes),
+                M.use_umi ? (", passes_mapq " + std::to_string(M.passes_mapq) + ", passes_umi " + std::to_string(M.passes_umi) + ", umi_column_bytes " + std::to_string(S.umi.bytes)).c_str() : "");
     return 0;
 }
 
@@ -166,8 +198,9 @@ namespace rsqc {
 void markdup_drop(rsqc_ctx *c) {
     MarkdupState &M = c->markdup;
     M.active = M.done = false;
-    M.n = 0; M.passes_lo = M.passes_hi = 0;
-    M.info = rsqc_markdup_info{};
+    M.n = 0; M.passes_lo = M.passes_hi = M.passes_mapq = M.passes_umi = 0;
+    M.use_umi = false;
+    M.info = rsqc_markdup_info{}; M.umi_info = rsqc_markdup_umi_info{};
     M.verdict.release();
     M.h_verdict.clear(); M.h_verdict.shrink_to_fit();
 }
@@ -175,13 +208,14 @@ void markdup_drop(rsqc_ctx *c) {
 // called by rsqc_sort_end on the complete collection (the stream has been synchronised), before its key reduction
 int markdup_run(rsqc_ctx *c) {
     MarkdupState &M = c->markdup;
-    M.info = rsqc_markdup_info{};
+    M.info = rsqc_markdup_info{}; M.umi_info = rsqc_markdup_umi_info{};
     M.info.records = M.n = c->sort.n;
     if (M.n == 0) { M.done = true; return 0; }
     Scratch X;
     const int rc = markdup_stage(c, X);
     if (rc) (void)hipStreamSynchronize(c->stream);
     X.release();                                       // everything but the verdict column goes before the coordinate sort allocates
+    c->sort.umi.release(); c->sort.cap_umi = 0;        // ... the collection's UMI column with it: the gather into output batches never sees it
     if (rc) return rc;
     M.done = true;
     return 0;
@@ -198,6 +232,25 @@ int rsqc_markdup_begin(rsqc_ctx *c) {
         return fail(c, RSQC_ERR_ARG, "rsqc_markdup_begin must precede the first submit of the pass");
     markdup_drop(c);
     c->markdup.active = true;
+    return RSQC_OK;
+}
+
+int rsqc_markdup_use_umi(rsqc_ctx *c) {
+    if (!c) return RSQC_ERR_ARG;
+    if (c->sticky) return c->sticky;
+    if (!c->markdup.active || c->markdup.done) return fail(c, RSQC_ERR_ARG, "rsqc_markdup_begin must precede rsqc_markdup_use_umi");
+    if (c->name_mode >= 0 || c->sort.batches_in || c->sort.n)
+        return fail(c, RSQC_ERR_ARG, "rsqc_markdup_use_umi must precede the first submit of the pass");
+    c->markdup.use_umi = true;
+    return RSQC_OK;
+}
+
+int rsqc_markdup_umi_end(rsqc_ctx *c, rsqc_markdup_umi_info *out) {
+    if (!c || !out) return RSQC_ERR_ARG;
+    if (c->sticky) return c->sticky;
+    if (!c->markdup.active || !c->markdup.use_umi) return fail(c, RSQC_ERR_ARG, "rsqc_markdup_use_umi must precede rsqc_markdup_umi_end");
+    if (!c->markdup.done) return fail(c, RSQC_ERR_ARG, "rsqc_sort_end must precede rsqc_markdup_umi_end");
+    *out = c->markdup.umi_info;
     return RSQC_OK;
 }
 

@@ -140,6 +140,7 @@ RSQC_BAM_FN uint32_t sam_parse_one(const SamWindow &S, uint32_t j) {
     if (rc != SAM_OK) return rc;
     o.core.cigar_off = at;
     W.core[j] = o.core; W.aux[j] = o.aux; W.qh2[j] = o.qhash2;
+    if (W.umi) W.umi[j] = o.umi;
     S.rtid[j] = o.tid;
     return SAM_OK;
 }

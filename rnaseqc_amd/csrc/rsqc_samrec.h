@@ -195,6 +195,8 @@ RSQC_BAM_FN uint32_t sam_parse_fields(const uint8_t *s, uint32_t len, const uint
     // optional fields TG:T:value; the last occurrence of a tag decides, as in bam_parse_record
     uint32_t tagbits = (tid == mtid) ? RSQC_TB_MTID_SAME : 0;
     int32_t nm = 0;
+    uint64_t umi = tags.umi_src == RSQC_UMI_QNAME ? umi_from_qname(s, qlen, tags.umi_sep) : 0ull;
+    bool umi_open = tags.umi_src == RSQC_UMI_TAG;                              // the first field of that name counts, as in bam_parse_record
     for (uint32_t a = f[11]; a < len;) {
         uint32_t b = a;
         while (b < len && s[b] != '\t') ++b;
@@ -213,9 +215,13 @@ RSQC_BAM_FN uint32_t sam_parse_fields(const uint8_t *s, uint32_t len, const uint
         }
         for (uint32_t fi = 0; fi < tags.n_filter; ++fi)                         // GetTag: Z, integer or float
             if (t0 == (char)tags.f0[fi] && t1 == (char)tags.f1[fi] && (type == 'Z' || type == 'f' || is_int)) tagbits |= (uint32_t)RSQC_TB_FILTER0 << fi;
+        if (umi_open && t0 == (char)tags.umi_t0 && t1 == (char)tags.umi_t1) {
+            umi_open = false;
+            if (type == 'Z') umi = umi_pack(v, vl);
+        }
         a = b + 1;
     }
-    o.qname_len = qlen; o.qhash2 = bam_qh2_finish(qh2, qlen);
+    o.qname_len = qlen; o.qhash2 = bam_qh2_finish(qh2, qlen); o.umi = umi;
     o.core.pos = pos; o.core.mpos = mpos; o.core.isize = (int32_t)isize; o.core.cigar_off = 0;
     o.aux.qhash = qh; o.aux.flag = (uint16_t)flag; o.aux.mapq = (uint8_t)mapq;
     o.tid = tid; o.n_ops = n_ops; o.ops_off = 0;

@@ -196,9 +196,9 @@ namespace rsqc {
 
 void sort_drop(rsqc_ctx *c) {
     SortState &S = c->sort;
-    for (DevBuf *b : {&S.core, &S.aux, &S.qh2, &S.key, &S.cigar, &S.wide_index, &S.wide_nm, &S.wide_lq, &S.wide_nc}) b->release();
+    for (DevBuf *b : {&S.core, &S.aux, &S.qh2, &S.key, &S.cigar, &S.wide_index, &S.wide_nm, &S.wide_lq, &S.wide_nc, &S.umi}) b->release();
     S.active = false;
-    S.n = S.n_ops = S.n_wide = S.cap_n = S.cap_ops = S.cap_wide = S.batches_in = 0;
+    S.n = S.n_ops = S.n_wide = S.cap_n = S.cap_ops = S.cap_wide = S.cap_umi = S.batches_in = 0;
     S.batch_rec0.clear(); S.batch_pool0.clear();
 }
 
@@ -211,6 +211,10 @@ static int sort_append_run(rsqc_ctx *c, UploadedBatch *u) {
     {
         DevBuf *cols[4] = {&S.core, &S.aux, &S.qh2, &S.key}; const size_t width[4] = {16, 16, 4, 8};
         if ((rc = grow_columns(c, cols, width, 4, S.n, S.n + u->n, S.cap_n, "the record columns"))) return rc;
+    }
+    if (c->markdup.use_umi) {                          // the UMI keys: a column of its own, so that the record columns are what they are without the mode
+        DevBuf *cols[1] = {&S.umi}; const size_t width[1] = {8};
+        if ((rc = grow_columns(c, cols, width, 1, S.n, S.n + u->n, S.cap_umi, "the UMI column"))) return rc;
     }
     {
         DevBuf *cols[1] = {&S.cigar}; const size_t width[1] = {4};
@@ -225,6 +229,7 @@ static int sort_append_run(rsqc_ctx *c, UploadedBatch *u) {
     HIP_TRY(c, hipMemcpyAsync((char *)S.core.p + S.n * 16, d.core, (size_t)u->n * 16, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync((char *)S.aux.p + S.n * 16, d.aux, (size_t)u->n * 16, hipMemcpyDeviceToDevice, c->stream));
     if (d.qhash2) HIP_TRY(c, hipMemcpyAsync((char *)S.qh2.p + S.n * 4, d.qhash2, (size_t)u->n * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (c->markdup.use_umi) HIP_TRY(c, hipMemcpyAsync((char *)S.umi.p + S.n * 8, u->umi, (size_t)u->n * 8, hipMemcpyDeviceToDevice, c->stream));
     if (u->n_cigar_total) HIP_TRY(c, hipMemcpyAsync((char *)S.cigar.p + S.n_ops * 4, d.cigar, (size_t)u->n_cigar_total * 4, hipMemcpyDeviceToDevice, c->stream));
     launch_sort_append(c->stream, d.core, u->n, d.seg_tid, d.seg_start, d.n_seg, (uint64_t *)S.key.p + S.n, S.n, d.wide_index, d.wide_nm, d.wide_l_qseq, d.wide_n_cigar, d.n_wide,
                        (uint64_t *)S.wide_index.p + S.n_wide, (int32_t *)S.wide_nm.p + S.n_wide, (int32_t *)S.wide_lq.p + S.n_wide, (uint32_t *)S.wide_nc.p + S.n_wide);

@@ -168,6 +168,9 @@ static int upload_batch(rsqc_ctx *c, const rsqc_batch *b, UploadedBatch *u, bool
     UP(wide_index, b->n_wide); UP(wide_nm, b->n_wide); UP(wide_l_qseq, b->n_wide); UP(wide_n_cigar, b->n_wide);
     d.qhash2 = nullptr;
     if (b->qhash2) UP(qhash2, b->n);
+    // rsqc_batch.umi: read only while the context marks duplicates by UMI (rsqc_markdup_use_umi); never dereferenced otherwise
+    u->umi = nullptr;
+    if (b->umi && c->markdup.use_umi && (rc = upload(c, u->bufs, b->umi, (size_t)b->n, &u->umi, pooled))) return rc;
     d.seg_file_index = nullptr;
     u->seg_file_index.clear(); u->seg_records.clear();
     if (b->seg_file_index && b->n_seg) {
@@ -255,6 +258,8 @@ int run_batch(rsqc_ctx *c, UploadedBatch *u) {
     if (!c->have_ann) return fail(c, RSQC_ERR_ARG, "rsqc_set_annotation must precede rsqc_submit");
     if (c->finalized) return fail(c, RSQC_ERR_ARG, "rsqc_reset required after rsqc_finalize");
     if (u->n == 0) return 0;
+    if (c->sort.active && c->markdup.use_umi && !u->umi)       // (refused for what it is: the collection stays as it was)
+        return fail(c, RSQC_ERR_ARG, "rsqc_batch.umi must be given for every batch of a pass behind rsqc_markdup_use_umi");
     // one name identity per pass: a fragment whose mates carry (qhash, h2) and (qhash, 0) would count as two names
     {
         const int mode = u->d.qhash2 ? 1 : 0;

@@ -76,6 +76,10 @@ def load_library():
         lib.rsqc_markdup_begin.argtypes = [vp]
         lib.rsqc_markdup_end.argtypes = [vp, C.POINTER(abi.MarkdupInfo)]
         lib.rsqc_markdup_verdicts.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+        lib.rsqc_markdup_use_umi.argtypes = [vp]
+        lib.rsqc_markdup_umi_end.argtypes = [vp, C.POINTER(abi.MarkdupUmiInfo)]
+        lib.rsqc_umi_pack.restype = C.c_uint64
+        lib.rsqc_umi_pack.argtypes = [C.c_char_p, C.c_uint32]
         lib.rsqc_junctions_begin.argtypes = [vp]
         lib.rsqc_junctions_end.argtypes = [vp, C.POINTER(abi.JunctionTable)]
         lib.rsqc_track_begin.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_char_p)]
@@ -96,7 +100,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_group_create", "rsqc_group_reduce", "rsqc_group_info", "rsqc_group_destroy", "rsqc_refresh_results", "rsqc_finalize_device", "rsqc_host_alloc", "rsqc_host_free", "rsqc_strerror",
     "rsqc_last_error", "rsqc_counter_name", "rsqc_version", "rsqc_qname_hash", "rsqc_qname_hash2",
     "rsqc_decode_begin", "rsqc_decode_submit", "rsqc_decode_end", "rsqc_decode_begin_sam", "rsqc_decode_submit_text",
-    "rsqc_sort_begin", "rsqc_sort_end", "rsqc_markdup_begin", "rsqc_markdup_end", "rsqc_markdup_verdicts", "rsqc_junctions_begin", "rsqc_junctions_end",
+    "rsqc_sort_begin", "rsqc_sort_end", "rsqc_markdup_begin", "rsqc_markdup_end", "rsqc_markdup_verdicts", "rsqc_markdup_use_umi", "rsqc_markdup_umi_end", "rsqc_umi_pack", "rsqc_junctions_begin", "rsqc_junctions_end",
     "rsqc_track_begin", "rsqc_track_end", "rsqc_track_rows", "rsqc_track_text",
     "rsqc_genebody_begin", "rsqc_genebody_end", "rsqc_genebody_sums",
 ]
@@ -177,10 +181,21 @@ class Engine:
         self._check(self._l.rsqc_wait(self._h))
 
     # ---- device-side BAM decode (rsqc_decode_*) -----------------------------------------------------------------
-    def decode_begin(self, n_ref, ch_tag="ch", filter_tags=(), file_index_base=0, pipelined=False, reserve=0, ref_names=None):
+    def decode_begin(self, n_ref, ch_tag="ch", filter_tags=(), file_index_base=0, pipelined=False, reserve=0, ref_names=None, umi_tag=None, umi_qname=None):
         """ref_names (the SAM header's @SQ names, n_ref of them): a SAM text stream (rsqc_decode_begin_sam), fed with
-        decode_submit_text (plain SAM) or decode_submit (BGZF-compressed SAM); None: a BAM stream."""
+        decode_submit_text (plain SAM) or decode_submit (BGZF-compressed SAM); None: a BAM stream.
+        umi_tag ("RX") or umi_qname (the separator, "_"): the windows get a umi column (rsqc_decode_params.umi_source)."""
         p = abi.DecodeParams()
+        if umi_tag is not None and umi_qname is not None:
+            raise ValueError("one UMI source: umi_tag or umi_qname")
+        if umi_tag is not None:
+            if len(umi_tag) != 2:
+                raise ValueError("umi_tag is two characters")
+            p.umi_source = abi.UMI_SOURCE_TAG; p.umi_tag = umi_tag.encode()
+        if umi_qname is not None:
+            if len(umi_qname) != 1:
+                raise ValueError("umi_qname is one character")
+            p.umi_source = abi.UMI_SOURCE_QNAME; p.umi_sep = umi_qname.encode()
         p.pipelined = 1 if pipelined else 0
         p.reserve_inflated_bytes = reserve
         p.n_ref = n_ref
@@ -270,6 +285,25 @@ class Engine:
         p = C.c_void_p()
         self._check(self._l.rsqc_markdup_verdicts(self._h, int(first), int(n), C.byref(p)))
         return abi._view(p.value, int(n), np.uint8)
+
+    def markdup_use_umi(self):
+        """Behind markdup_begin(), before the first submit: the UMI key (Batch.umi / the decode stream's umi column) joins the signature."""
+        self._check(self._l.rsqc_markdup_use_umi(self._h))
+
+    def markdup_umi_end(self) -> dict:
+        """Behind sort_end() of a pass with markdup_use_umi(): the fields of rsqc_markdup_umi_info."""
+        info = abi.MarkdupUmiInfo()
+        self._check(self._l.rsqc_markdup_umi_end(self._h, C.byref(info)))
+        return {f: int(getattr(info, f)) for f, _ in abi.MarkdupUmiInfo._fields_}
+
+    def last_window_umi(self) -> np.ndarray:
+        """The umi column of the window the last decode_submit / decode_submit_text decoded (a non-pipelined stream with a UMI
+        source), copied from the device through rsqc_decode_window.device_batch.umi."""
+        w = self._last_window
+        n = int(w.n_records)
+        if n and not w.device_batch.umi:
+            raise EngineError(abi.ERR_ARG, "the window has no umi column")
+        return self.read_device(w.device_batch.umi, n, np.uint64)
 
     # ---- reads per splice junction (rsqc_junctions_*) -------------------------------------------------------------
     def junctions_begin(self):
@@ -510,3 +544,9 @@ def run_engine(params, ann, batches, bed=None, owned=None, reference=None) -> ab
         return e.finalize()
     finally:
         e.close()
+
+
+def umi_pack(umi) -> int:
+    """The product's own rsqc_umi_pack (abi.umi_pack is the same definition in Python)."""
+    b = umi.encode() if isinstance(umi, str) else bytes(umi)
+    return int(load_library().rsqc_umi_pack(b, len(b)))

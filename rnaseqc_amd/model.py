@@ -259,6 +259,7 @@ class Batch:
     file_index_base: int = 0
     qhash2: np.ndarray | None = None      # rsqc_batch.qhash2 (second name hash, uint32 per record); None = the 64-bit identity
     seg_file_index: np.ndarray | None = None   # rsqc_batch.seg_file_index: the batch is several file ranges, one per segment (uint64 per segment)
+    umi: np.ndarray | None = None         # rsqc_batch.umi (abi.umi_pack of every record's UMI, uint64; 0 = none): read only behind rsqc_markdup_use_umi
 
     _DT = dict(pos=np.int32, mpos=np.int32, isize=np.int32, qhash=np.uint64, cigar_off=np.uint32,
                flag=np.uint16, l_qseq=np.uint16, mapq=np.uint8, nm=np.uint8, tagbits=np.uint8,
@@ -312,6 +313,10 @@ class Batch:
             self.seg_file_index = np.ascontiguousarray(self.seg_file_index, dtype=np.uint64)
             assert len(self.seg_file_index) == len(self.seg_tid)
             s.seg_file_index = abi.ptr(self.seg_file_index)
+        if self.umi is not None:
+            self.umi = np.ascontiguousarray(self.umi, dtype=np.uint64)
+            assert len(self.umi) == self.n
+            s.umi = abi.ptr(self.umi)
         return s
 
     # ---------------------------------------------------------------- builders
@@ -415,7 +420,8 @@ class Batch:
                      wide_index=np.concatenate([(p.wide_index.astype(np.int64) + n_at[k]) for k, p in enumerate(parts)]).astype(np.uint64),
                      wide_nm=cat("wide_nm"), wide_l_qseq=cat("wide_l_qseq"), wide_n_cigar=cat("wide_n_cigar"),
                      file_index_base=parts[0].file_index_base,
-                     qhash2=(np.concatenate([p.qhash2 for p in parts]) if all(p.qhash2 is not None for p in parts) else None), **kw)
+                     qhash2=(np.concatenate([p.qhash2 for p in parts]) if all(p.qhash2 is not None for p in parts) else None),
+                     umi=(np.concatenate([p.umi for p in parts]) if all(p.umi is not None for p in parts) else None), **kw)
 
     @staticmethod
     def concat_ranges(parts: Sequence["Batch"]) -> "Batch":
@@ -484,7 +490,8 @@ class Batch:
                      wide_index=np.array([w[0] for w in wsel], np.uint64), wide_nm=self.wide_nm[[w[1] for w in wsel]] if wsel else np.zeros(0, np.int32),
                      wide_l_qseq=self.wide_l_qseq[[w[1] for w in wsel]] if wsel else np.zeros(0, np.int32),
                      wide_n_cigar=self.wide_n_cigar[[w[1] for w in wsel]] if wsel else np.zeros(0, np.uint32),
-                     qhash2=(self.qhash2[idx] if self.qhash2 is not None else None), **kw)
+                     qhash2=(self.qhash2[idx] if self.qhash2 is not None else None),
+                     umi=(np.asarray(self.umi)[idx] if self.umi is not None else None), **kw)
 
     def coordinate_sorted(self) -> "Batch":
         """Stable sort by (contig, position), unplaced records last: what a coordinate-sorted BAM holds."""
@@ -523,4 +530,5 @@ class Batch:
                      wide_index=(self.wide_index[wm] - lo).astype(np.uint64), wide_nm=self.wide_nm[wm].copy(),
                      wide_l_qseq=self.wide_l_qseq[wm].copy(), wide_n_cigar=self.wide_n_cigar[wm].copy(),
                      file_index_base=self.file_index_base + lo,
-                     qhash2=(self.qhash2[lo:hi].copy() if self.qhash2 is not None else None), **kw)
+                     qhash2=(self.qhash2[lo:hi].copy() if self.qhash2 is not None else None),
+                     umi=(np.asarray(self.umi)[lo:hi].copy() if self.umi is not None else None), **kw)

@@ -184,9 +184,11 @@ def make_reads(ann: Annotation, n_pairs: int, seed: int = 2, read_len: int = 150
                expr_sigma: float = 2.0, low_mapq_frac: float = 0.05, secondary_frac: float = 0.01,
                supplementary_frac: float = 0.005, unmapped_frac: float = 0.01, indel_frac: float = 0.02,
                chimeric_tag_frac: float = 0.0, filter_tag_frac: float = 0.0, expr_genes: int | None = None,
-               contig_lengths=None, only_contig: int | None = None, fid_base: int = 0) -> Batch:
+               contig_lengths=None, only_contig: int | None = None, fid_base: int = 0, umi_bases: int = 0) -> Batch:
     """fid_base: first fragment number (QNAMEs are "SYN:%012d" of the fragment number), so that batches made
-    contig by contig (make_reads_sharded) never share a name."""
+    contig by contig (make_reads_sharded) never share a name.
+    umi_bases (1..31): the batch gets a umi column -- one random UMI of that many bases per FRAGMENT (every record of the
+    fragment carries it), drawn from a generator of its own: every other column is what it is without the option."""
     rng = np.random.default_rng(seed)
     rl = read_len
     G = ann.n_genes_listed
@@ -469,6 +471,12 @@ def make_reads(ann: Annotation, n_pairs: int, seed: int = 2, read_len: int = 150
     if keep_qnames:
         b.qname = digits.reshape(-1).copy()
         b.qname_off = (np.arange(N + 1, dtype=np.uint32) * 16).astype(np.uint32)
+    if umi_bases:
+        if not 1 <= umi_bases <= abi.UMI_MAX_BASES:
+            raise ValueError("umi_bases: 1..%d" % abi.UMI_MAX_BASES)
+        local = (fid - fid.min()).astype(np.int64) if N else np.zeros(0, np.int64)
+        per_fragment = np.random.default_rng([seed, 0x554D49]).integers(0, 1 << (2 * umi_bases), int(local.max()) + 1 if N else 0, dtype=np.uint64)
+        b.umi = (np.uint64(1 << (2 * umi_bases)) | per_fragment[local]).astype(np.uint64)
     return b
 
 
