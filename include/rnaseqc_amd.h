@@ -703,7 +703,7 @@ RSQC_API int rsqc_markdup_verdicts(rsqc_ctx *ctx, uint64_t first, uint64_t n, co
  * becomes (tid, u5, rev, mrev, kind, w, umi), umi being the anchor RECORD's own key in rsqc_batch.umi (rsqc_umi_pack); the mate's key is
  * never consulted.  Anchors with key 0 (no usable UMI) form sets among themselves: an anchor without a UMI is never a duplicate of one
  * that has one.  Survivor, verdicts and the name rule are unchanged.  tests/markdup_umi_ref.py is the executable form.
- *   limits       UMIs match exactly (no grouping of UMIs one mismatch apart); only the anchor's UMI counts; a UMI has at most 31 bases;
+ *   limits       UMIs match exactly (unless rsqc_markdup_umi_edits, below, groups UMIs one substitution apart); only the anchor's UMI counts; a UMI has at most 31 bases;
  *                an N (any byte other than A C G T in either case and the joiners - and +) voids the UMI: key 0.
  * rsqc_markdup_use_umi: behind rsqc_markdup_begin and before the pass's first submit (RSQC_ERR_ARG otherwise).  Every batch of the
  * pass must then carry rsqc_batch.umi (see there).  rsqc_markdup_umi_end: behind rsqc_sort_end of such a pass (RSQC_ERR_ARG otherwise);
@@ -722,6 +722,45 @@ typedef struct rsqc_markdup_umi_info {
 } rsqc_markdup_umi_info;
 RSQC_API int rsqc_markdup_use_umi(rsqc_ctx *ctx);
 RSQC_API int rsqc_markdup_umi_end(rsqc_ctx *ctx, rsqc_markdup_umi_info *out);
+
+/* ---- UMIs one substitution apart grouped before marking (additive to ABI 7: two functions and one struct) -----------------------
+ * rsqc_markdup_umi_edits(ctx, 1) changes the contract of rsqc_markdup_use_umi in ONE point: the signature's last component is the ROOT
+ * of the anchor's UMI, not the UMI itself.  In integers (tests/markdup_umi_group_ref.py is the executable form; no equality with
+ * UMI-tools, fgbio or samtools markdup --barcode-* is claimed):
+ *   nodes        a position set P is the set of anchors with equal (tid, u5, rev, mrev, kind, w).  Inside P a node is one distinct UMI
+ *                key k; its count c(k) is the number of ANCHORS (not records) of P that carry k.  Key 0 is a node too: it has no
+ *                neighbours, never gets a parent and is never one.
+ *   neighbours   two non-zero keys of the same number of bases L that differ in exactly one base: k' = k ^ (x << 2j), x in {1, 2, 3},
+ *                0 <= j < L.  Keys of different L are never neighbours: no insertions or deletions.  The joiners are gone from the
+ *                key: ACGT-TGCA is 8 bases, one substitution allowed anywhere in them.
+ *   eligible     a neighbour p of k in the SAME P is an eligible parent when c(p) >= 2 c(k) - 1 (the `directional` threshold, in 64
+ *                bits) AND (c(p) > c(k), or c(p) == c(k) and p < k as integers).  Equal counts pass the first test only at c = 1; the
+ *                second test makes the relation acyclic.
+ *   parent       the eligible neighbour with the highest count, ties to the smallest key; without one, k is a root.
+ *   root         root(k) follows parents to a root; the signature is P + (root(k),).  Survivor (the highest mapq, the earliest arrival
+ *                on ties, over ALL anchors of the grouped set, whichever node they came from), verdicts by name, population, anchors,
+ *                flag rewriting and cleared_records are unchanged.
+ *   figures      rsqc_markdup_info.sets and .duplicate_fragments are those of the grouped signature; rsqc_markdup_umi_info is
+ *                unchanged (position_duplicate_fragments does not depend on grouping).  umi_nodes: nodes over all position sets;
+ *                merged_nodes: nodes with a parent; exact_duplicate_fragments = anchors - umi_nodes: what exact matching would have
+ *                called; group_ms: host clock around the grouping kernels.  duplicate_fragments == exact_duplicate_fragments +
+ *                merged_nodes and position_duplicate_fragments >= duplicate_fragments >= exact_duplicate_fragments are checked after
+ *                read-back (RSQC_ERR_HIP otherwise).
+ *   limits       edit distance 1 only, substitutions only; the anchor's UMI only; one parent per node, chosen locally (UMI-tools'
+ *                directional method searches from the highest count down and may assign a node otherwise).
+ * rsqc_markdup_umi_edits: behind rsqc_markdup_use_umi and before the pass's first submit; max_edits is 0 (exact matching: no launch,
+ * allocation or output differs from a pass without the call) or 1; RSQC_ERR_ARG otherwise.  rsqc_markdup_umi_group_end: behind
+ * rsqc_sort_end of a pass with max_edits 1 (RSQC_ERR_ARG otherwise); a second call returns the same figures without device work.
+ * Memory with max_edits 1: 16 more bytes per anchor during the stage (68 instead of 52: the position marks, which become the final
+ * marks, and three node columns sized by the anchor count); the other node columns -- 28 bytes per node: key, best anchor, group's
+ * best anchor, parent, root -- live in buffers the sort is done with.  All of it goes with the stage's other buffers.  rsqc_reset,
+ * rsqc_clear_inputs and rsqc_destroy end the mode.                                                                                  */
+typedef struct rsqc_markdup_umi_group_info {
+    uint64_t umi_nodes, merged_nodes, exact_duplicate_fragments;
+    double   group_ms;
+} rsqc_markdup_umi_group_info;
+RSQC_API int rsqc_markdup_umi_edits(rsqc_ctx *ctx, uint32_t max_edits);
+RSQC_API int rsqc_markdup_umi_group_end(rsqc_ctx *ctx, rsqc_markdup_umi_group_info *out);
 
 /* ---- reads per splice junction (additive to ABI 6) ---------------------------------------------------------------------
  * Between rsqc_junctions_begin and the end of the pass every batch that the per-read kernels run also leaves its splice-junction

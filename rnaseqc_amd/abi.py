@@ -204,6 +204,10 @@ class MarkdupUmiInfo(C.Structure):
     _fields_ = [("anchors_with_umi", C.c_uint64), ("anchors_without_umi", C.c_uint64), ("position_duplicate_fragments", C.c_uint64)]
 
 
+class MarkdupUmiGroupInfo(C.Structure):
+    _fields_ = [("umi_nodes", C.c_uint64), ("merged_nodes", C.c_uint64), ("exact_duplicate_fragments", C.c_uint64), ("group_ms", C.c_double)]
+
+
 class JunctionTable(C.Structure):
     _fields_ = [("n", C.c_uint64), ("instances", C.c_uint64), ("population", C.c_uint64),
                 ("tid", _P), ("start", _P), ("end", _P), ("reads", _P), ("hq_reads", _P), ("max_overhang", _P),

@@ -60,6 +60,8 @@ struct Options {
     // --umi-tag=XX / --umi-qname[=C] (extensions, each implies --mark-duplicates): the UMI joins the duplicate signature (rsqc_markdup_use_umi);
     // the tag's two letters / the separator in front of the UMI at the end of the read name, as given (checked at validation)
     bool has_umi_tag = false, has_umi_qname = false; std::string umi_tag, umi_sep = "_";
+    // --umi-edits=N (extension; with one of the two above): 1 groups UMIs one substitution apart before marking (rsqc_markdup_umi_edits); as given
+    bool has_umi_edits = false; std::string umi_edits = "0";
     bool sort = false;                 // --sort (extension): input in any order, put in coordinate order on the GPU (rsqc_sort_begin / rsqc_sort_end)
 };
 
@@ -97,6 +99,7 @@ void usage(std::ostream &o) {
          "      --mark-duplicates                 (extension) Flag duplicate fragments on the GPU before they are counted: implies --sort, replaces the input's 0x400 flags (one GPU, one input)\n"
          "      --umi-tag=[XX]                    (extension) UMI-aware --mark-duplicates (implied): the UMI is the Z value of aux tag XX (e.g. RX); exact match, the anchor's UMI, 31 bases at most, N voids it\n"
          "      --umi-qname=[C]                   (extension) The same with the UMI taken from the read name, behind its last C. Default: _ (use : for bcl-convert names)\n"
+         "      --umi-edits=[N]                   (extension) With --umi-tag / --umi-qname: 1 merges UMIs of one position that are one substitution apart (towards the higher count, count >= 2 x - 1) before marking. Default: 0, exact match\n"
          "      --junctions                       (extension) Count reads per splice junction on the GPU and write [sample].junctions.tsv (one GPU)\n"
          "      --bedgraph                        (extension) Build the per-base coverage track on the GPU and write [sample].coverage.bedgraph (one GPU; needs LN in the header)\n"
          "      --gene-body                       (extension) Sum the coverage along every gene's body, 5' to 3' in 100 bins, on the GPU and write [sample].gene_body.tsv (one GPU; needs LN in the header)\n";
@@ -182,6 +185,7 @@ Options parse(int argc, char **argv) {
         else if (name == "mark-duplicates") o.mark_duplicates = o.sort = true;
         else if (name == "umi-tag") { o.umi_tag = need(); o.has_umi_tag = o.mark_duplicates = o.sort = true; }
         else if (name == "umi-qname") { if (has_value) o.umi_sep = value; o.has_umi_qname = o.mark_duplicates = o.sort = true; }
+        else if (name == "umi-edits") { o.umi_edits = need(); o.has_umi_edits = true; }
         else if (name == "junctions") o.junctions = true;
         else if (name == "bedgraph") o.bedgraph = true;
         else if (name == "gene-body") o.gene_body = true;
@@ -805,6 +809,7 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     if (o.mark_duplicates && (rc = rsqc_markdup_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --umi-tag / --umi-qname: the UMI key of the decode streams / the host reader's batches joins the signature
     if ((o.has_umi_tag || o.has_umi_qname) && (rc = rsqc_markdup_use_umi(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    if (o.umi_edits == "1" && (rc = rsqc_markdup_umi_edits(gpu, 1)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --junctions: every batch the per-read kernels run leaves its junction instances on the device (under --sort: the sorted batches)
     if (o.junctions && (rc = rsqc_junctions_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --bedgraph: and its coverage events, in a difference array over the header's contigs (kept by the context while it is large enough)
@@ -916,6 +921,10 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if ((o.has_umi_tag || o.has_umi_qname) && rc == RSQC_OK && (rc = rsqc_markdup_umi_end(gpu, &mu)) == RSQC_OK && o.verbosity)
             cout << "UMIs in the signature: anchors_with_umi " << mu.anchors_with_umi << ", anchors_without_umi " << mu.anchors_without_umi
                  << ", position_duplicate_fragments " << mu.position_duplicate_fragments << endl;
+        rsqc_markdup_umi_group_info mg{};
+        if (o.umi_edits == "1" && rc == RSQC_OK && (rc = rsqc_markdup_umi_group_end(gpu, &mg)) == RSQC_OK && o.verbosity)
+            cout << "UMIs grouped: umi_nodes " << mg.umi_nodes << ", merged_nodes " << mg.merged_nodes << ", exact_duplicate_fragments " << mg.exact_duplicate_fragments
+                 << ", group_ms " << mg.group_ms << endl;
     }
     rsqc_results res{};
     if (rc == RSQC_OK) rc = rsqc_finalize(gpu, &res);
@@ -1268,6 +1277,8 @@ int main(int argc, char **argv) {
         if (o.has_umi_tag && o.has_umi_qname) throw ValidationError("--umi-tag and --umi-qname name two sources of the UMI: give one");
         if (o.has_umi_tag && o.umi_tag.size() != 2) throw ValidationError("--umi-tag takes the two characters of an aux tag (e.g. RX)");
         if (o.has_umi_qname && o.umi_sep.size() != 1) throw ValidationError("--umi-qname takes one separator character (default _)");
+        if (o.has_umi_edits && o.umi_edits != "0" && o.umi_edits != "1") throw ValidationError("--umi-edits takes 0 (exact match) or 1 (UMIs one substitution apart are merged)");
+        if (o.has_umi_edits && !o.has_umi_tag && !o.has_umi_qname) throw ValidationError("--umi-edits needs the source of the UMI: --umi-tag or --umi-qname");
         if (o.mark_duplicates) {
             // the whole input must be resident: the stage runs on the collection of --sort, in ONE context
             if (o.has_bam_list) throw ValidationError("--mark-duplicates takes one input (it cannot be combined with --bam-list)");

@@ -161,6 +161,8 @@ struct MarkdupState {
     bool use_umi = false;                              // rsqc_markdup_use_umi: the UMI key is part of the signature
     int passes_mapq = 0, passes_umi = 0;               // ... and the live passes of its two extra sort stages
     rsqc_markdup_umi_info umi_info{};
+    uint32_t umi_edits = 0;                            // rsqc_markdup_umi_edits: 1 = UMIs one substitution apart are grouped before marking
+    rsqc_markdup_umi_group_info group_info{};
     DevBuf verdict;
     std::vector<uint8_t> h_verdict;                    // the window of the last rsqc_markdup_verdicts
 };

@@ -29,6 +29,16 @@
 //    byte: below it, anchors of one signature and UMI but different mapq would not be adjacent)
 //   markdup_heads_umi_kernel   1 where signature AND key are the predecessor's; beside it the number of anchors whose signature alone
 //                              is the predecessor's -- what the marking without the UMI would have called (position_duplicate_fragments)
+//
+// rsqc_markdup_umi_edits(1) (--umi-edits=1): the last component is the ROOT of the anchor's UMI -- UMIs of one position set that are one
+// substitution apart merge towards the higher count (the contract: include/rnaseqc_amd.h, tests/markdup_umi_group_ref.py).  Five more
+// kernels between the heads and the list, every kernel above unchanged:
+//   markdup_heads_pos_kernel      1 where the position signature alone is the predecessor's; with the marks above and two scans every
+//                                 rank knows its node (a distinct UMI of a position set) and its set
+//   markdup_group_nodes_kernel    head ranks write the node columns: key, head rank (counts are differences), best anchor, set
+//   markdup_group_parents_kernel  the hot one: per node 3 L neighbour keys, each a binary search among the nodes of its own set
+//   markdup_group_roots_kernel    parent[] walked to the root (into a separate column), the node's best anchor merged into the root's
+//   markdup_group_marks_kernel    per rank: a duplicate unless it is its group's best anchor; then the scan and the list as ever
 #pragma once
 
 #if !defined(RSQC_WAVE_EMU)
@@ -228,6 +238,121 @@ __global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_heads_umi_kernel(cons
     if (threadIdx.x == 0 && pm) atomicAdd(&counters[4], (unsigned long long)pm);
 }
 
+// ---- rsqc_markdup_umi_edits(1): the signature's last component is the ROOT of the anchor's UMI ------------------------------------
+// Ranks are in the order above, so a position set is a run of ranks and its distinct UMIs -- the NODES -- ascend inside it.  at / at_pos:
+// the exclusive prefix sums of markdup_heads_umi_kernel's marks and of the position marks below, tot[0] / tot[1] their sums.  A rank
+// whose sum does not move on behind it is a head; the node of rank r is r - (the sum through r), its set likewise.
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_heads_pos_kernel(const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, uint64_t n, uint32_t *mark_pos) {
+    const uint64_t r = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    if (r >= n) return;
+    uint32_t same = 0u;
+    if (r > 0 && key[r] == key[r - 1]) {
+        const uint32_t s = idx[r], p = idx[r - 1];
+        if (s < n && p < n && (k_lo[s] >> 8) == (k_lo[p] >> 8)) same = 1u;
+    }
+    mark_pos[r] = same;
+}
+// the head rank of a node writes its columns: the key, the rank itself (node_head; the count of node m is node_head[m + 1] -
+// node_head[m], node_head[n_nodes] = n), its set, and node_best = ((255 - mapq) << 32) | slot of the head anchor -- the order makes the
+// head the node's best anchor, slots are in arrival order.  A set's head writes set_first[set]; set_first[n_sets] = n_nodes
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_group_nodes_kernel(const uint32_t *at, const uint32_t *at_pos, const unsigned long long *tot, const uint32_t *idx, const uint64_t *k_lo,
+                                                                               const uint64_t *k_umi, uint64_t n, uint64_t *node_key, uint32_t *node_head, uint64_t *node_best, uint32_t *node_set,
+                                                                               uint32_t *set_first, unsigned long long *group_best) {
+    const uint64_t r = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    if (r >= n || tot[0] >= n || tot[1] >= n) return;
+    const uint32_t n_nodes = (uint32_t)(n - tot[0]), n_sets = (uint32_t)(n - tot[1]);
+    if (r == 0) { node_head[n_nodes] = (uint32_t)n; set_first[n_sets] = n_nodes; }
+    const uint32_t before = at[r], through = r + 1 < n ? at[r + 1] : (uint32_t)tot[0];
+    if (through != before) return;                     // not a head
+    const uint32_t before_pos = at_pos[r], through_pos = r + 1 < n ? at_pos[r + 1] : (uint32_t)tot[1];
+    const uint32_t node = (uint32_t)r - before, set = (uint32_t)r - through_pos;
+    if (node >= n_nodes || set >= n_sets) return;      // (never: a store is not let out of the columns)
+    const uint32_t s = idx[r];
+    node_key[node] = s < n ? k_umi[s] : 0ull;
+    node_best[node] = s < n ? ((k_lo[s] & 0xFFull) << 32) | (uint64_t)s : ~0ull;
+    node_head[node] = (uint32_t)r; node_set[node] = set;
+    group_best[node] = ~0ull;
+    if (through_pos == before_pos) set_first[set] = node;
+}
+// the node that holds key q in node_key[lo, hi) (ascending), or RSQC_MD_EMPTY
+__device__ inline uint32_t md_find_node(const uint64_t *node_key, uint32_t lo, uint32_t hi, uint64_t q) {
+    const uint32_t end = hi;
+    while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); if (node_key[m] < q) lo = m + 1; else hi = m; }
+    return (lo < end && node_key[lo] == q) ? lo : RSQC_MD_EMPTY;
+}
+// one lane per node: the 3 L keys one substitution from its own -- k ^ (x << 2j), never the length bit -- are looked up in the nodes
+// of ITS set only (a smaller key in front of the node, a larger one behind it).  parent = the eligible neighbour with the highest
+// count, ties to the smallest key; eligible: count(p) >= 2 count(k) - 1 in 64 bits, and count(p) > count(k) or equal with p < k.
+// Key 0 has no neighbours.  counters[5] += nodes with a parent, [6] += nodes, [7] += keys looked up: one atomic per workgroup each
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_group_parents_kernel(const uint64_t *node_key, const uint32_t *node_head, const uint32_t *node_set, const uint32_t *set_first,
+                                                                                 uint32_t n_nodes, uint32_t n_sets, uint32_t *parent, unsigned long long *counters) {
+    const uint64_t nd64 = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    uint32_t best = RSQC_MD_EMPTY, probes = 0;
+    if (nd64 < n_nodes) {
+        const uint32_t nd = (uint32_t)nd64, set = node_set[nd];
+        const uint64_t k = node_key[nd];
+        if (k != 0 && set < n_sets) {
+            const uint32_t lo = set_first[set], hi = set_first[set + 1] < n_nodes ? set_first[set + 1] : n_nodes;
+            if (lo <= nd && nd < hi && hi - lo > 1) {
+                const uint32_t c = node_head[nd + 1] - node_head[nd];
+                const uint64_t need = 2ull * c - 1ull;
+                const uint32_t L = (uint32_t)(63 - __builtin_clzll(k)) >> 1;
+                uint32_t best_c = 0; uint64_t best_key = 0;
+                for (uint32_t j = 0; j < L; ++j)
+                    for (uint64_t x = 1; x < 4; ++x) {
+                        const uint64_t q = k ^ (x << (2 * j));
+                        const uint32_t m = q < k ? md_find_node(node_key, lo, nd, q) : md_find_node(node_key, nd + 1, hi, q);
+                        if (m == RSQC_MD_EMPTY) continue;
+                        const uint32_t cp = node_head[m + 1] - node_head[m];
+                        if ((uint64_t)cp >= need && (cp > c || (cp == c && q < k)) && (cp > best_c || (cp == best_c && q < best_key))) { best = m; best_c = cp; best_key = q; }
+                    }
+                probes = 3 * L;
+            }
+        }
+        parent[nd] = best;
+    }
+    uint32_t merged = 0, nodes = 0, looked = 0;
+    (void)md_block_scan(best != RSQC_MD_EMPTY ? 1u : 0u, merged);
+    (void)md_block_scan(nd64 < n_nodes ? 1u : 0u, nodes);
+    (void)md_block_scan(probes, looked);
+    if (threadIdx.x == 0) {
+        if (merged) atomicAdd(&counters[5], (unsigned long long)merged);
+        if (nodes) atomicAdd(&counters[6], (unsigned long long)nodes);
+        if (looked) atomicAdd(&counters[7], (unsigned long long)looked);
+    }
+}
+// every node walks parent[] (read only: nothing is written in place, so nothing races) to its root -- at most as many steps as its set
+// has nodes -- writes root[] and merges its best anchor into the root's: group_best[] is all ones before the kernel
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_group_roots_kernel(const uint32_t *parent, const uint32_t *node_set, const uint32_t *set_first, const uint64_t *node_best,
+                                                                               uint32_t n_nodes, uint32_t n_sets, uint32_t *root, unsigned long long *group_best) {
+    const uint64_t nd = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    if (nd >= n_nodes) return;
+    const uint32_t set = node_set[nd];
+    const uint32_t size = set < n_sets ? set_first[set + 1] - set_first[set] : 0u;
+    uint32_t r = (uint32_t)nd;
+    for (uint32_t step = 0; step < size; ++step) { const uint32_t p = parent[r]; if (p >= n_nodes) break; r = p; }
+    root[nd] = r;
+    // a 64-bit minimum as a compare-and-swap loop (the first guess is the value the column starts with): the one 64-bit atomic besides
+    // the add that the kernels of this file are written against
+    const unsigned long long v = (unsigned long long)node_best[nd];
+    unsigned long long old = ~0ull;
+    while (v < old) { const unsigned long long seen = atomicCAS(&group_best[r], old, v); if (seen == old) break; old = seen; }
+}
+// per rank: a duplicate exactly when the anchor is not the best of its root's group.  These marks take the way of the plain ones
+__global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_group_marks_kernel(const uint32_t *at, const unsigned long long *tot, const uint32_t *idx, const uint64_t *k_lo, const uint32_t *root,
+                                                                               const unsigned long long *group_best, uint64_t n, uint32_t n_nodes, uint32_t *mark) {
+    const uint64_t r = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
+    if (r >= n) return;
+    const uint32_t through = r + 1 < n ? at[r + 1] : (uint32_t)tot[0];
+    const uint32_t node = (uint32_t)r - through, s = idx[r];
+    uint32_t dup = 0u;
+    if (s < n && node < n_nodes) {
+        const uint32_t rt = root[node];
+        if (rt < n_nodes) dup = ((((k_lo[s] & 0xFFull) << 32) | (uint64_t)s) != group_best[rt]) ? 1u : 0u;
+    }
+    mark[r] = dup;
+}
+
 // ---- stage 5: the names of the duplicate anchors; table: mask + 1 slots, all RSQC_MD_EMPTY --------------------------------------
 __global__ __launch_bounds__(RSQC_MD_THREADS) void markdup_insert_kernel(MarkdupCollection C, const uint32_t *dup_list, uint64_t n_dup, uint32_t *table, uint32_t mask) {
     const uint64_t j = (uint64_t)blockIdx.x * RSQC_MD_THREADS + threadIdx.x;
@@ -283,6 +408,15 @@ void launch_markdup_heads(hipStream_t s, const uint64_t *key, const uint32_t *id
 void launch_markdup_list(hipStream_t s, const uint32_t *at, const unsigned long long *total, const uint32_t *idx, const uint32_t *ci, uint64_t n, uint32_t *dup_list);
 void launch_markdup_umi_keys(hipStream_t s, const MarkdupCollection &C, const uint32_t *ci, uint64_t n_anchors, uint64_t *k_umi, unsigned long long *counters);
 void launch_markdup_heads_umi(hipStream_t s, const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, const uint64_t *k_umi, uint64_t n, uint32_t *mark, unsigned long long *counters);
+void launch_markdup_heads_pos(hipStream_t s, const uint64_t *key, const uint32_t *idx, const uint64_t *k_lo, uint64_t n, uint32_t *mark_pos);
+void launch_markdup_group_nodes(hipStream_t s, const uint32_t *at, const uint32_t *at_pos, const unsigned long long *tot, const uint32_t *idx, const uint64_t *k_lo, const uint64_t *k_umi, uint64_t n,
+                                uint64_t *node_key, uint32_t *node_head, uint64_t *node_best, uint32_t *node_set, uint32_t *set_first, unsigned long long *group_best);
+void launch_markdup_group_parents(hipStream_t s, const uint64_t *node_key, const uint32_t *node_head, const uint32_t *node_set, const uint32_t *set_first, uint32_t n_nodes, uint32_t n_sets,
+                                  uint32_t *parent, unsigned long long *counters);
+void launch_markdup_group_roots(hipStream_t s, const uint32_t *parent, const uint32_t *node_set, const uint32_t *set_first, const uint64_t *node_best, uint32_t n_nodes, uint32_t n_sets, uint32_t *root,
+                                unsigned long long *group_best);
+void launch_markdup_group_marks(hipStream_t s, const uint32_t *at, const unsigned long long *tot, const uint32_t *idx, const uint64_t *k_lo, const uint32_t *root, const unsigned long long *group_best,
+                                uint64_t n, uint32_t n_nodes, uint32_t *mark);
 void launch_markdup_insert(hipStream_t s, const MarkdupCollection &C, const uint32_t *dup_list, uint64_t n_dup, uint32_t *table, uint32_t mask);
 void launch_markdup_apply(hipStream_t s, const MarkdupCollection &C, const uint32_t *dup_list, uint64_t n_dup, const uint32_t *table, uint32_t mask, uint8_t *verdict, unsigned long long *counters);
 #endif

@@ -28,8 +28,9 @@ int alloc_or_capacity(rsqc_ctx *c, DevBuf &b, size_t bytes, const char *what, ui
 struct Scratch {
     DevBuf batch_tab, block_anchors, counters, totals, chunk_sum, k_hi, k_lo, ci, key0, key1, idx0, idx1, hist, part, table;
     DevBuf k_umi;                                      // rsqc_markdup_use_umi only: the anchors' UMI keys by slot
-    size_t bytes() { size_t n = 0; for (DevBuf *b : {&batch_tab, &block_anchors, &counters, &totals, &chunk_sum, &k_hi, &k_lo, &ci, &key0, &key1, &idx0, &idx1, &hist, &part, &table, &k_umi}) n += b->bytes; return n; }
-    void release() { for (DevBuf *b : {&batch_tab, &block_anchors, &counters, &totals, &chunk_sum, &k_hi, &k_lo, &ci, &key0, &key1, &idx0, &idx1, &hist, &part, &table, &k_umi}) b->release(); }
+    DevBuf g_mark, g_head, g_set, g_first;             // rsqc_markdup_umi_edits(1) only: position marks (then the final marks), node head ranks, node sets, first node of a set
+    size_t bytes() { size_t n = 0; for (DevBuf *b : {&batch_tab, &block_anchors, &counters, &totals, &chunk_sum, &k_hi, &k_lo, &ci, &key0, &key1, &idx0, &idx1, &hist, &part, &table, &k_umi, &g_mark, &g_head, &g_set, &g_first}) n += b->bytes; return n; }
+    void release() { for (DevBuf *b : {&batch_tab, &block_anchors, &counters, &totals, &chunk_sum, &k_hi, &k_lo, &ci, &key0, &key1, &idx0, &idx1, &hist, &part, &table, &k_umi, &g_mark, &g_head, &g_set, &g_first}) b->release(); }
 };
 
 int markdup_stage(rsqc_ctx *c, Scratch &X) {
@@ -81,6 +82,8 @@ int markdup_stage(rsqc_ctx *c, Scratch &X) {
             (rc = alloc_or_capacity(c, X.idx1, A * 4 + 64, "the sort's second index column", A)) || (rc = alloc_or_capacity(c, X.hist, 256 * tiles * 4 + 64, "the digit histograms", A)) ||
             (rc = alloc_or_capacity(c, X.chunk_sum, scan_chunks * 8, "the scan's chunk sums", A)) || (rc = alloc_or_capacity(c, X.part, (size_t)prep_grid * (M.use_umi ? 72 : 48), "the key reduction", A)) ||
             (M.use_umi && (rc = alloc_or_capacity(c, X.k_umi, A * 8 + 64, "the UMI key column", A)))) return rc;
+        if (M.umi_edits && ((rc = alloc_or_capacity(c, X.g_mark, A * 4 + 64, "the position marks of the UMI grouping", A)) || (rc = alloc_or_capacity(c, X.g_head, A * 4 + 64, "the node heads of the UMI grouping", A)) ||
+                            (rc = alloc_or_capacity(c, X.g_set, A * 4 + 64, "the node sets of the UMI grouping", A)) || (rc = alloc_or_capacity(c, X.g_first, A * 4 + 64, "the set starts of the UMI grouping", A)))) return rc;
         d_chunk = (unsigned long long *)X.chunk_sum.p;
         uint64_t *kbuf[2] = {(uint64_t *)X.key0.p, (uint64_t *)X.key1.p};
         uint32_t *ibuf[2] = {(uint32_t *)X.idx0.p, (uint32_t *)X.idx1.p};
@@ -146,14 +149,62 @@ int markdup_stage(rsqc_ctx *c, Scratch &X) {
         // ---- 4 heads: the marks take the payload's free buffer, D the keys' free buffer
         t0 = std::chrono::steady_clock::now();
         uint32_t *mark = ibuf[ic ^ 1], *list = (uint32_t *)kbuf[kc ^ 1];
+        double heads_ms = 0;                           // (rsqc_markdup_umi_edits: the heads kernel, clocked apart from the grouping)
         if (M.use_umi) launch_markdup_heads_umi(c->stream, kbuf[kc], ibuf[ic], k_lo, k_umi, A, mark, d_cnt);
         else launch_markdup_heads(c->stream, kbuf[kc], ibuf[ic], k_lo, A, mark);
+        if (M.umi_edits) {
+            // ---- 4b rsqc_markdup_umi_edits(1): nodes, parents, roots, and marks that replace the plain ones.  The columns take buffers the
+            // sort is done with: the node keys the keys' free buffer (D follows them there), the nodes' best anchors the sorted K_hi, the
+            // groups' best anchors K_hi by slot, parents and roots the two halves of the UMI keys by slot (read last by the nodes kernel)
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            HIP_TRY(c, hipGetLastError());
+            heads_ms = ms_since(t0);
+            const bool profile = getenv("RSQC_MARKDUP_PROFILE") != nullptr;
+            double part_ms[5] = {0, 0, 0, 0, 0};
+            auto tg = std::chrono::steady_clock::now(), tk = tg;
+            auto lap = [&](int k) {                        // the profile's split by kernel: a synchronisation behind each (an error stays for the one below)
+                if (!profile) return;
+                (void)hipStreamSynchronize(c->stream);
+                part_ms[k] = ms_since(tk); tk = std::chrono::steady_clock::now();
+            };
+            uint32_t *mark_pos = (uint32_t *)X.g_mark.p, *node_head = (uint32_t *)X.g_head.p, *node_set = (uint32_t *)X.g_set.p, *set_first = (uint32_t *)X.g_first.p;
+            uint64_t *node_key = kbuf[kc ^ 1], *node_best = kbuf[kc];
+            unsigned long long *group_best = (unsigned long long *)X.k_hi.p;
+            uint32_t *parent = (uint32_t *)X.k_umi.p, *root = parent + A;
+            launch_markdup_heads_pos(c->stream, kbuf[kc], ibuf[ic], k_lo, A, mark_pos);
+            launch_sort_scan(c->stream, mark, A, d_chunk, d_tot + 1);
+            launch_sort_scan(c->stream, mark_pos, A, d_chunk, d_tot + 2);
+            unsigned long long tot[2] = {0, 0};
+            HIP_TRY(c, hipMemcpyAsync(tot, d_tot + 1, 16, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            HIP_TRY(c, hipGetLastError());
+            if (tot[0] >= A || tot[1] >= A || tot[0] > tot[1]) return fail(c, RSQC_ERR_HIP, "rsqc_sort_end: the node marks of the UMI grouping do not add up");
+            const uint32_t n_nodes = (uint32_t)(A - tot[0]), n_sets = (uint32_t)(A - tot[1]);
+            lap(0);
+            launch_markdup_group_nodes(c->stream, mark, mark_pos, d_tot + 1, ibuf[ic], k_lo, k_umi, A, node_key, node_head, node_best, node_set, set_first, group_best);
+            lap(1);
+            launch_markdup_group_parents(c->stream, node_key, node_head, node_set, set_first, n_nodes, n_sets, parent, d_cnt);
+            lap(2);
+            launch_markdup_group_roots(c->stream, parent, node_set, set_first, node_best, n_nodes, n_sets, root, group_best);
+            lap(3);
+            launch_markdup_group_marks(c->stream, mark, d_tot + 1, ibuf[ic], k_lo, root, group_best, A, n_nodes, mark_pos);
+            lap(4);
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            HIP_TRY(c, hipGetLastError());
+            M.group_info.group_ms = ms_since(tg);
+            M.group_info.umi_nodes = n_nodes; M.group_info.exact_duplicate_fragments = tot[0];
+            if (profile)
+                fprintf(stderr, "markdup group: nodes %u, sets %u, heads_scans_ms %.3f, nodes_ms %.3f, parents_ms %.3f, roots_ms %.3f, marks_ms %.3f, device_bytes %llu\n", n_nodes, n_sets, part_ms[0],
+                        part_ms[1], part_ms[2], part_ms[3], part_ms[4], (unsigned long long)(X.bytes() + M.verdict.bytes));
+            t0 = std::chrono::steady_clock::now();
+            mark = mark_pos;                           // the final marks; the scanned plain ones are done with
+        }
         launch_sort_scan(c->stream, mark, A, d_chunk, d_tot);
         launch_markdup_list(c->stream, mark, d_tot, ibuf[ic], (const uint32_t *)X.ci.p, A, list);
         HIP_TRY(c, hipMemcpyAsync(&n_dup, d_tot, 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
-        info.mark_ms = ms_since(t0);
+        info.mark_ms = heads_ms + ms_since(t0);
         if (n_dup >= A) return fail(c, RSQC_ERR_HIP, "rsqc_sort_end: the head marks of the duplicate marking do not add up");
         d_list = list;
     }
@@ -172,8 +223,8 @@ int markdup_stage(rsqc_ctx *c, Scratch &X) {
         launch_markdup_insert(c->stream, C, d_list, n_dup, (uint32_t *)X.table.p, mask);
     }
     launch_markdup_apply(c->stream, C, d_list, n_dup, n_dup ? (const uint32_t *)X.table.p : nullptr, mask, (uint8_t *)M.verdict.p, d_cnt);
-    unsigned long long cnt[5] = {0, 0, 0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, 40, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, M.umi_edits ? 64 : 40, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     info.mark_ms += ms_since(t0);
@@ -181,6 +232,13 @@ int markdup_stage(rsqc_ctx *c, Scratch &X) {
     if (M.use_umi) {
         if (cnt[3] > A || cnt[4] >= std::max<unsigned long long>(A, 1) || cnt[4] < n_dup) return fail(c, RSQC_ERR_HIP, "rsqc_sort_end: the UMI figures of the duplicate marking do not add up");
         M.umi_info.anchors_with_umi = cnt[3]; M.umi_info.anchors_without_umi = A - cnt[3]; M.umi_info.position_duplicate_fragments = cnt[4];
+    }
+    if (M.umi_edits && A) {
+        rsqc_markdup_umi_group_info &G = M.group_info;
+        G.merged_nodes = cnt[5];
+        if (cnt[6] != G.umi_nodes || n_dup != G.exact_duplicate_fragments + G.merged_nodes || cnt[4] < n_dup || n_dup < G.exact_duplicate_fragments)
+            return fail(c, RSQC_ERR_HIP, "rsqc_sort_end: the figures of the UMI grouping do not add up");
+        if (getenv("RSQC_MARKDUP_PROFILE")) fprintf(stderr, "markdup group: merged_nodes %llu, probes %llu\n", cnt[5], cnt[7]);
     }
     // RSQC_MARKDUP_PROFILE: what the sort stages had to move (tools/markdup_bench.py) -- key + payload, read and written once per pass
     // and what the stage holds on the device at its end, the verdict column included (nothing is freed before)
@@ -199,8 +257,8 @@ void markdup_drop(rsqc_ctx *c) {
     MarkdupState &M = c->markdup;
     M.active = M.done = false;
     M.n = 0; M.passes_lo = M.passes_hi = M.passes_mapq = M.passes_umi = 0;
-    M.use_umi = false;
-    M.info = rsqc_markdup_info{}; M.umi_info = rsqc_markdup_umi_info{};
+    M.use_umi = false; M.umi_edits = 0;
+    M.info = rsqc_markdup_info{}; M.umi_info = rsqc_markdup_umi_info{}; M.group_info = rsqc_markdup_umi_group_info{};
     M.verdict.release();
     M.h_verdict.clear(); M.h_verdict.shrink_to_fit();
 }
@@ -208,7 +266,7 @@ void markdup_drop(rsqc_ctx *c) {
 // called by rsqc_sort_end on the complete collection (the stream has been synchronised), before its key reduction
 int markdup_run(rsqc_ctx *c) {
     MarkdupState &M = c->markdup;
-    M.info = rsqc_markdup_info{}; M.umi_info = rsqc_markdup_umi_info{};
+    M.info = rsqc_markdup_info{}; M.umi_info = rsqc_markdup_umi_info{}; M.group_info = rsqc_markdup_umi_group_info{};
     M.info.records = M.n = c->sort.n;
     if (M.n == 0) { M.done = true; return 0; }
     Scratch X;
@@ -242,6 +300,26 @@ int rsqc_markdup_use_umi(rsqc_ctx *c) {
     if (c->name_mode >= 0 || c->sort.batches_in || c->sort.n)
         return fail(c, RSQC_ERR_ARG, "rsqc_markdup_use_umi must precede the first submit of the pass");
     c->markdup.use_umi = true;
+    return RSQC_OK;
+}
+
+int rsqc_markdup_umi_edits(rsqc_ctx *c, uint32_t max_edits) {
+    if (!c) return RSQC_ERR_ARG;
+    if (c->sticky) return c->sticky;
+    if (!c->markdup.active || c->markdup.done || !c->markdup.use_umi) return fail(c, RSQC_ERR_ARG, "rsqc_markdup_use_umi must precede rsqc_markdup_umi_edits");
+    if (c->name_mode >= 0 || c->sort.batches_in || c->sort.n)
+        return fail(c, RSQC_ERR_ARG, "rsqc_markdup_umi_edits must precede the first submit of the pass");
+    if (max_edits > 1) return fail(c, RSQC_ERR_ARG, "rsqc_markdup_umi_edits: max_edits is 0 or 1, not " + std::to_string(max_edits));
+    c->markdup.umi_edits = max_edits;
+    return RSQC_OK;
+}
+
+int rsqc_markdup_umi_group_end(rsqc_ctx *c, rsqc_markdup_umi_group_info *out) {
+    if (!c || !out) return RSQC_ERR_ARG;
+    if (c->sticky) return c->sticky;
+    if (!c->markdup.active || !c->markdup.use_umi || !c->markdup.umi_edits) return fail(c, RSQC_ERR_ARG, "rsqc_markdup_umi_edits(1) must precede rsqc_markdup_umi_group_end");
+    if (!c->markdup.done) return fail(c, RSQC_ERR_ARG, "rsqc_sort_end must precede rsqc_markdup_umi_group_end");
+    *out = c->markdup.group_info;
     return RSQC_OK;
 }
 

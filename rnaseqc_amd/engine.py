@@ -78,6 +78,8 @@ def load_library():
         lib.rsqc_markdup_verdicts.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]
         lib.rsqc_markdup_use_umi.argtypes = [vp]
         lib.rsqc_markdup_umi_end.argtypes = [vp, C.POINTER(abi.MarkdupUmiInfo)]
+        lib.rsqc_markdup_umi_edits.argtypes = [vp, C.c_uint32]
+        lib.rsqc_markdup_umi_group_end.argtypes = [vp, C.POINTER(abi.MarkdupUmiGroupInfo)]
         lib.rsqc_umi_pack.restype = C.c_uint64
         lib.rsqc_umi_pack.argtypes = [C.c_char_p, C.c_uint32]
         lib.rsqc_junctions_begin.argtypes = [vp]
@@ -100,7 +102,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_group_create", "rsqc_group_reduce", "rsqc_group_info", "rsqc_group_destroy", "rsqc_refresh_results", "rsqc_finalize_device", "rsqc_host_alloc", "rsqc_host_free", "rsqc_strerror",
     "rsqc_last_error", "rsqc_counter_name", "rsqc_version", "rsqc_qname_hash", "rsqc_qname_hash2",
     "rsqc_decode_begin", "rsqc_decode_submit", "rsqc_decode_end", "rsqc_decode_begin_sam", "rsqc_decode_submit_text",
-    "rsqc_sort_begin", "rsqc_sort_end", "rsqc_markdup_begin", "rsqc_markdup_end", "rsqc_markdup_verdicts", "rsqc_markdup_use_umi", "rsqc_markdup_umi_end", "rsqc_umi_pack", "rsqc_junctions_begin", "rsqc_junctions_end",
+    "rsqc_sort_begin", "rsqc_sort_end", "rsqc_markdup_begin", "rsqc_markdup_end", "rsqc_markdup_verdicts", "rsqc_markdup_use_umi", "rsqc_markdup_umi_end", "rsqc_markdup_umi_edits", "rsqc_markdup_umi_group_end", "rsqc_umi_pack", "rsqc_junctions_begin", "rsqc_junctions_end",
     "rsqc_track_begin", "rsqc_track_end", "rsqc_track_rows", "rsqc_track_text",
     "rsqc_genebody_begin", "rsqc_genebody_end", "rsqc_genebody_sums",
 ]
@@ -295,6 +297,17 @@ class Engine:
         info = abi.MarkdupUmiInfo()
         self._check(self._l.rsqc_markdup_umi_end(self._h, C.byref(info)))
         return {f: int(getattr(info, f)) for f, _ in abi.MarkdupUmiInfo._fields_}
+
+    def markdup_umi_edits(self, max_edits: int):
+        """Behind markdup_use_umi(), before the first submit: 1 groups UMIs of one position set that are one substitution apart
+        (rsqc_markdup_umi_edits); 0 is exact matching."""
+        self._check(self._l.rsqc_markdup_umi_edits(self._h, int(max_edits)))
+
+    def markdup_umi_group_end(self) -> dict:
+        """Behind sort_end() of a pass with markdup_umi_edits(1): the fields of rsqc_markdup_umi_group_info (group_ms a float)."""
+        info = abi.MarkdupUmiGroupInfo()
+        self._check(self._l.rsqc_markdup_umi_group_end(self._h, C.byref(info)))
+        return {f: (float if f == "group_ms" else int)(getattr(info, f)) for f, _ in abi.MarkdupUmiGroupInfo._fields_}
 
     def last_window_umi(self) -> np.ndarray:
         """The umi column of the window the last decode_submit / decode_submit_text decoded (a non-pipelined stream with a UMI
