@@ -867,6 +867,55 @@ RSQC_API int rsqc_genebody_begin(rsqc_ctx *ctx, int32_t n_genes, const uint32_t 
 RSQC_API int rsqc_genebody_end(rsqc_ctx *ctx, rsqc_genebody_info *out);
 RSQC_API int rsqc_genebody_sums(rsqc_ctx *ctx, uint32_t first_gene, uint32_t n, const uint64_t **sums);
 
+/* ---- per-gene transcript integrity from the coverage track (additive to ABI 7) ----------------------------------------------
+ * Behind rsqc_track_end the track's array holds the depth of every reference position; rsqc_tin_end walks every gene's model
+ * positions and leaves, per gene, the four figures that the evenness of its coverage (TIN = 100 * exp(H) / L, H the Shannon
+ * entropy of the depth along the gene) is made of -- two kernels at the end of the pass, no per-read kernel and no launch of a
+ * pass without the calls changes.  No equality with RSeQC's tin.py is claimed: every model position counts here.  The contract:
+ *   model        the model of rsqc_genebody_begin without the `reverse` byte (the figures are symmetric in the strand): gene g
+ *                owns rows [seg_off[g], seg_off[g + 1]) of (seg_tid, seg_start, seg_end), 0-based with end exclusive, all on one
+ *                contig of the track and inside [0, length[tid]), non-empty, ascending and disjoint; abutting rows are allowed; a
+ *                gene may have no row.  L is the sum of the segment lengths.  A gene is measured when L >= 1.
+ *   depth        depth(p) is the track's: population, CIGAR rules and clipping are those of rsqc_track_*.
+ *   row          rsqc_tin_row of every gene (all zero for L = 0), over its model positions p:
+ *                depth_sum = S = sum of depth(p); covered = the positions with depth(p) > 0; max_depth = the largest depth(p) --
+ *                all three exact; dlog2d = E = sum of depth(p) * log2(depth(p)) over the positions with depth(p) >= 2 (depths 0
+ *                and 1 contribute exactly 0).  Genes that share positions each see the full depth.
+ *   the double   E is reproducible: the order of its additions is fixed (a lane adds its positions in order, the wave combines its
+ *                lanes with a fixed butterfly, every plan item writes its partial to a slot of its own, a gene's items are added
+ *                in item order; no floating atomic), so on one device two passes over the same records give bit-identical E in
+ *                any record order, with any batch cuts, under rsqc_sort_begin and with RSQC_TRACK_MERGE 0 or 1.  Against the
+ *                exactly rounded sum its relative error is at most (items_g + 80) * 2^-52, items_g = ceil(L / 4096); E = 0 is
+ *                exact.
+ *   info         n_genes; n_measured: genes with L >= 1; model_bases: the sum of L; depth_sum: the sum of S; covered_bases: the
+ *                sum of covered (both added on the host from the rows); tin_ms: HIP events around the stage's kernels.
+ *   TIN          with H = ln(S) - E * ln(2) / S:  tin = 100 * exp(H) / L.  Uniform coverage gives 100, one covered base 100 / L,
+ *                depth 1 on C positions 100 * C / L.  (The command line prints it for genes with L >= 100 and S >= L.)
+ * rsqc_tin_begin: behind rsqc_track_begin of the same pass and before the pass's first submit (RSQC_ERR_ARG otherwise), in any
+ * order relative to rsqc_genebody_begin: both may be active in one pass, each with model buffers of its own.  It validates the
+ * model rules (a violation is RSQC_ERR_ARG with a message that names the gene and the rule; the pass goes on without the mode),
+ * builds the launch plan on the host -- every measured gene's [0, L) cut into items of at most 4096 model bases -- and uploads
+ * model and plan; a device refusal is RSQC_ERR_CAPACITY with the sizes.  Memory beyond the track's, on the device: 24 bytes per
+ * gene (the rows), 24 bytes per item (the partials), 12 bytes per segment (the model), and the plan's 20 bytes per item and 8 bytes
+ * per gene; on the host 24 page-locked bytes per gene.  rsqc_tin_end: behind rsqc_track_end (RSQC_ERR_ARG otherwise); a second
+ * call returns the same figures without device work; a failure voids the pass until rsqc_reset and never leaves partial rows.
+ * rsqc_tin_rows: the rows of genes [first_gene, first_gene + n), behind rsqc_tin_end: a window into page-locked memory that the
+ * context owns, valid until the mode ends; a window out of range is RSQC_ERR_ARG.  rsqc_reset, rsqc_clear_inputs and
+ * rsqc_destroy end the mode; rsqc_reset keeps the allocations.  Not exchanged by rsqc_reduce_* / rsqc_group_*.                   */
+typedef struct rsqc_tin_row {
+    uint64_t depth_sum;
+    uint32_t covered, max_depth;
+    double dlog2d;
+} rsqc_tin_row;
+typedef struct rsqc_tin_info {
+    uint64_t n_genes, n_measured, model_bases, depth_sum, covered_bases;
+    double tin_ms;
+} rsqc_tin_info;
+RSQC_API int rsqc_tin_begin(rsqc_ctx *ctx, int32_t n_genes, const uint32_t *seg_off /*[n_genes+1]*/,
+                            const int32_t *seg_tid, const uint32_t *seg_start, const uint32_t *seg_end);
+RSQC_API int rsqc_tin_end(rsqc_ctx *ctx, rsqc_tin_info *out);
+RSQC_API int rsqc_tin_rows(rsqc_ctx *ctx, uint32_t first_gene, uint32_t n, const rsqc_tin_row **rows);
+
 RSQC_API const char *rsqc_strerror(int code);
 RSQC_API const char *rsqc_last_error(rsqc_ctx *ctx);
 RSQC_API const char *rsqc_counter_name(int counter);   /* the reference's Metrics key  */

@@ -226,6 +226,15 @@ class GenebodyInfo(C.Structure):
     _fields_ = [("n_genes", C.c_uint64), ("n_measured", C.c_uint64), ("model_bases", C.c_uint64), ("depth_sum", C.c_uint64), ("bins_ms", C.c_double)]
 
 
+class TinInfo(C.Structure):
+    _fields_ = [("n_genes", C.c_uint64), ("n_measured", C.c_uint64), ("model_bases", C.c_uint64), ("depth_sum", C.c_uint64), ("covered_bases", C.c_uint64),
+                ("tin_ms", C.c_double)]
+
+
+# rsqc_tin_row, 24 bytes
+TIN_ROW = np.dtype([("depth_sum", np.uint64), ("covered", np.uint32), ("max_depth", np.uint32), ("dlog2d", np.float64)])
+
+
 def ptr(a: np.ndarray | None):
     """numpy array -> void* (None -> NULL).  The caller keeps `a` alive."""
     if a is None:

@@ -92,6 +92,21 @@ HAPI int host_write_junctions(const char *gtf, const char *out_path, const char 
     return 0;
 }
 
+// --tin: the host arithmetic on lengths and rows given as columns.  tin, mean_depth: [n]; stats: eligible, mean, median, stdev.
+// With paths (either may be NULL) the two files are written as the command line writes them; ids: n gene ids.  0, or 8 when a
+// file could not be written
+HAPI int host_tin_profile(uint64_t n, const uint32_t *gene_len, const rsqc_tin_row *rows, double *tin, double *mean_depth, double *stats,
+                          const char *const *ids, const char *tin_path, const char *summary_path) {
+    const TinProfile p = tin_profile(gene_len, (size_t)n, rows);
+    for (size_t g = 0; g < (size_t)n; ++g) { tin[g] = p.tin[g]; mean_depth[g] = p.mean_depth[g]; }
+    stats[0] = (double)p.eligible; stats[1] = p.mean; stats[2] = p.median; stats[3] = p.stdev;
+    std::vector<std::string> names;
+    for (size_t g = 0; ids && g < (size_t)n; ++g) names.emplace_back(ids[g]);
+    if (tin_path && ids && !write_tin(tin_path, names, gene_len, rows, p)) return 8;
+    if (summary_path && !write_tin_summary(summary_path, p)) return 8;
+    return 0;
+}
+
 HAPI unsigned host_library_complexity(double dup, double unique, double limit) { return library_complexity(dup, unique, limit); }
 
 struct BamHandle { BamReader reader; HostBatch batch; rsqc_batch view; std::vector<std::string> names; };

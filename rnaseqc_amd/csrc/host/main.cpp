@@ -55,6 +55,7 @@ struct Options {
     std::string bam_list; bool has_bam_list = false;   // --bam-list (extension): a cohort, the positionals are `gtf output`
     bool bedgraph = false;             // --bedgraph (extension): the per-base coverage track, <sample>.coverage.bedgraph (rsqc_track_begin / _end / _text)
     bool gene_body = false;            // --gene-body (extension): coverage along the gene body in 100 bins, <sample>.gene_body.tsv (rsqc_genebody_begin / _end / _sums; turns the track on)
+    bool tin = false;                  // --tin (extension): per-gene transcript integrity from the coverage track, <sample>.tin.tsv and <sample>.tin_summary.tsv (rsqc_tin_begin / _end / _rows; turns the track on)
     bool junctions = false;            // --junctions (extension): reads per splice junction, <sample>.junctions.tsv (rsqc_junctions_begin / rsqc_junctions_end)
     bool mark_duplicates = false;      // --mark-duplicates (extension, implies --sort): flag 0x400 rewritten on the GPU before the records are counted (rsqc_markdup_begin / rsqc_markdup_end)
     // --umi-tag=XX / --umi-qname[=C] (extensions, each implies --mark-duplicates): the UMI joins the duplicate signature (rsqc_markdup_use_umi);
@@ -102,7 +103,8 @@ void usage(std::ostream &o) {
          "      --umi-edits=[N]                   (extension) With --umi-tag / --umi-qname: 1 merges UMIs of one position that are one substitution apart (towards the higher count, count >= 2 x - 1) before marking. Default: 0, exact match\n"
          "      --junctions                       (extension) Count reads per splice junction on the GPU and write [sample].junctions.tsv (one GPU)\n"
          "      --bedgraph                        (extension) Build the per-base coverage track on the GPU and write [sample].coverage.bedgraph (one GPU; needs LN in the header)\n"
-         "      --gene-body                       (extension) Sum the coverage along every gene's body, 5' to 3' in 100 bins, on the GPU and write [sample].gene_body.tsv (one GPU; needs LN in the header)\n";
+         "      --gene-body                       (extension) Sum the coverage along every gene's body, 5' to 3' in 100 bins, on the GPU and write [sample].gene_body.tsv (one GPU; needs LN in the header)\n"
+         "      --tin                             (extension) Measure every gene's transcript integrity (TIN: the evenness of its coverage) on the GPU and write [sample].tin.tsv and [sample].tin_summary.tsv (one GPU; needs LN in the header)\n";
 }
 
 long to_long(const std::string &flag, const std::string &v) {
@@ -189,6 +191,7 @@ Options parse(int argc, char **argv) {
         else if (name == "junctions") o.junctions = true;
         else if (name == "bedgraph") o.bedgraph = true;
         else if (name == "gene-body") o.gene_body = true;
+        else if (name == "tin") o.tin = true;
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
         else if (name == "detection-threshold") o.detection = to_ulong(name, need());
         else throw ParseError("Flag could not be matched: " + name);
@@ -695,13 +698,14 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     if (sam_input && o.verbosity > 1) cout << "Input: " << input_format_name(in.fmt) << " (" << bam_contigs.size() << " @SQ lines), parsed on the GPU" << endl;
     if (o.verbosity > 1) cout << "Checking bam header..." << endl;
     if (!shares_contigs(S, ann, bam_contigs)) { cerr << S.prefix << "BAM file shares no contigs with GTF" << endl; return 11; }
-    if (o.bedgraph || o.gene_body)                     // the track needs every contig's length
+    if (o.bedgraph || o.gene_body || o.tin)            // the track needs every contig's length
         for (size_t k = 0; k < bam_contigs.size(); ++k)
-            if (k >= in.lengths.size() || in.lengths[k] == 0) { cerr << S.prefix << (o.bedgraph ? o.gene_body ? "--bedgraph and --gene-body need" : "--bedgraph needs" : "--gene-body needs") << " the length (LN) of every contig in the header: none for " << bam_contigs[k] << endl; return 10; }
+            if (k >= in.lengths.size() || in.lengths[k] == 0) { cerr << S.prefix << (o.tin ? o.bedgraph ? o.gene_body ? "--bedgraph, --gene-body and --tin need" : "--bedgraph and --tin need" : o.gene_body ? "--gene-body and --tin need" : "--tin needs"
+                                                                                      : o.bedgraph ? o.gene_body ? "--bedgraph and --gene-body need" : "--bedgraph needs" : "--gene-body needs") << " the length (LN) of every contig in the header: none for " << bam_contigs[k] << endl; return 10; }
     const bool same_header = S.flattened && bam_contigs == S.contigs;
     if (!same_header) flatten_for(S, ann, bam_contigs);
-    // --gene-body: the model of this header's contigs and lengths, built when either changes
-    if (o.gene_body && (!S.gene_body_built || S.gene_body_lengths != in.lengths)) { S.gene_body.build(ann, in.lengths); S.gene_body_lengths = in.lengths; S.gene_body_built = true; }
+    // --gene-body, --tin: the model of this header's contigs and lengths (one for both), built when either changes
+    if ((o.gene_body || o.tin) && (!S.gene_body_built || S.gene_body_lengths != in.lengths)) { S.gene_body.build(ann, in.lengths); S.gene_body_lengths = in.lengths; S.gene_body_built = true; }
     const int n_ref_bam = (int)bam_contigs.size();
 
     // ---- the context and its inputs
@@ -813,7 +817,7 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     // --junctions: every batch the per-read kernels run leaves its junction instances on the device (under --sort: the sorted batches)
     if (o.junctions && (rc = rsqc_junctions_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
     // --bedgraph: and its coverage events, in a difference array over the header's contigs (kept by the context while it is large enough)
-    if (o.bedgraph || o.gene_body) {
+    if (o.bedgraph || o.gene_body || o.tin) {
         std::vector<const char *> track_names;
         for (auto &nm : bam_contigs) track_names.push_back(nm.c_str());
         if ((rc = rsqc_track_begin(gpu, n_ref_bam, in.lengths.data(), track_names.data())) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
@@ -822,6 +826,13 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     if (o.gene_body) {
         const GeneBodyModel &m = S.gene_body;
         if ((rc = rsqc_genebody_begin(gpu, (int32_t)m.reverse.size(), m.seg_off.data(), m.seg_tid.data(), m.seg_start.data(), m.seg_end.data(), m.reverse.data())) != RSQC_OK) {
+            cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10;
+        }
+    }
+    // --tin: the same model without its strands, in buffers of the mode's own
+    if (o.tin) {
+        const GeneBodyModel &m = S.gene_body;
+        if ((rc = rsqc_tin_begin(gpu, (int32_t)m.gene_len.size(), m.seg_off.data(), m.seg_tid.data(), m.seg_start.data(), m.seg_end.data())) != RSQC_OK) {
             cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10;
         }
     }
@@ -931,11 +942,17 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     rsqc_junction_table junctions{};
     if (o.junctions && rc == RSQC_OK) rc = rsqc_junctions_end(gpu, &junctions);       // (ordered and reduced inside the timed window: the price of the flag)
     rsqc_track_info track{};
-    if ((o.bedgraph || o.gene_body) && rc == RSQC_OK) rc = rsqc_track_end(gpu, &track);      // (scan and rows inside the timed window as well)
+    if ((o.bedgraph || o.gene_body || o.tin) && rc == RSQC_OK) rc = rsqc_track_end(gpu, &track);      // (scan and rows inside the timed window as well)
     rsqc_genebody_info gene_body{};
     GeneBodyProfile gene_body_rows;
     if (o.gene_body && rc == RSQC_OK) rc = rsqc_genebody_end(gpu, &gene_body);               // (and the stage over the scanned array)
+    rsqc_tin_info tin{};
+    const rsqc_tin_row *tin_rows = nullptr;                // (the context's, until its next reset: the files are written below, before it)
+    TinProfile tin_values;
+    if (o.tin && rc == RSQC_OK) rc = rsqc_tin_end(gpu, &tin);                                // (and the two kernels of --tin)
     S.t_loop1 = Clock::now();
+    if (o.tin && rc == RSQC_OK && (rc = rsqc_tin_rows(gpu, 0, (uint32_t)tin.n_genes, &tin_rows)) == RSQC_OK)
+        tin_values = tin_profile(S.gene_body.gene_len.data(), S.gene_body.gene_len.size(), tin_rows);
     if (o.gene_body && rc == RSQC_OK) {
         // the report's part, like the track's text: the sums come from the context in one window and are folded into the file's 100 rows
         const uint64_t *sums = nullptr;
@@ -961,6 +978,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (o.gene_body)
             cout << "Gene body: genes " << gene_body.n_genes << ", measured " << gene_body.n_measured << ", eligible " << gene_body_rows.eligible << ", model_bases " << gene_body.model_bases
                  << ", depth_sum " << gene_body.depth_sum << ", bins_ms " << gene_body.bins_ms << endl;
+        if (o.tin)
+            cout << "TIN: genes " << tin.n_genes << ", measured " << tin.n_measured << ", eligible " << tin_values.eligible << ", model_bases " << tin.model_bases
+                 << ", covered_bases " << tin.covered_bases << ", depth_sum " << tin.depth_sum << ", median " << tin_values.median << ", tin_ms " << tin.tin_ms << endl;
         cout << "Estimating library complexity..." << endl;
         cout << "Generating report" << endl;
     }
@@ -980,6 +1000,11 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     }
     if (o.gene_body && !write_gene_body(out_dir + "/" + sample.name + ".gene_body.tsv", gene_body_rows)) {
         cerr << S.prefix << "Filesystem error:  cannot write " << out_dir << "/" << sample.name << ".gene_body.tsv" << endl; return 8;
+    }
+    if (o.tin) {
+        const std::string stem = out_dir + "/" + sample.name;
+        if (!write_tin(stem + ".tin.tsv", ann.gene_list, S.gene_body.gene_len.data(), tin_rows, tin_values)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".tin.tsv" << endl; return 8; }
+        if (!write_tin_summary(stem + ".tin_summary.tsv", tin_values)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".tin_summary.tsv" << endl; return 8; }
     }
     if (!S.async_reports) {
         S.t_rep0 = Clock::now();
@@ -1304,6 +1329,12 @@ int main(int argc, char **argv) {
             bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
             if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
             if (many_gpus) throw ValidationError("--gene-body runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
+        }
+        if (o.tin) {
+            // the stage reads ONE context's difference array, like --gene-body (the rows are contig-local, but the track is one-GPU)
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--tin runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
         }
         if (o.junctions) {
             // one table per context: the per-contig tables of shards would only need concatenating, but that path is not built

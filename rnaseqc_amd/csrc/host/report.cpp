@@ -485,4 +485,52 @@ bool write_gene_body(const std::string &path, const GeneBodyProfile &p) {
     return f.good();
 }
 
+TinProfile tin_profile(const uint32_t *gene_len, size_t n_genes, const rsqc_tin_row *rows) {
+    TinProfile p;
+    p.mean_depth.assign(n_genes, 0.0); p.tin.assign(n_genes, 0.0); p.is_eligible.assign(n_genes, 0);
+    std::vector<double> vals;
+    for (size_t g = 0; g < n_genes; ++g) {
+        const uint64_t L = gene_len[g], S = rows[g].depth_sum;
+        if (!L) continue;
+        p.mean_depth[g] = (double)S / (double)L;
+        if (L < 100 || S < L) continue;                    // (a mean depth below 1: the rule of --gene-body)
+        const double H = std::log((double)S) - rows[g].dlog2d * std::log(2.0) / (double)S;
+        p.tin[g] = 100.0 * std::exp(H) / (double)L;
+        p.is_eligible[g] = 1; ++p.eligible;
+        p.mean += p.tin[g];                                // (in gene order)
+        vals.push_back(p.tin[g]);
+    }
+    if (p.eligible) {
+        const double n = (double)p.eligible;
+        p.mean /= n;
+        double var = 0;
+        for (double v : vals) var += (v - p.mean) * (v - p.mean);
+        p.stdev = std::sqrt(var / n);
+        std::sort(vals.begin(), vals.end());
+        p.median = vals.size() % 2 ? vals[vals.size() / 2] : (vals[vals.size() / 2 - 1] + vals[vals.size() / 2]) / 2.0;
+    }
+    return p;
+}
+
+bool write_tin(const std::string &path, const std::vector<std::string> &gene_ids, const uint32_t *gene_len, const rsqc_tin_row *rows, const TinProfile &p) {
+    std::ofstream f(path);
+    f << "gene_id\tlength\tcovered\tdepth_sum\tmax_depth\tmean_depth\ttin" << NL;
+    char a[64], b[64];
+    for (size_t g = 0; g < p.tin.size(); ++g) {
+        snprintf(a, sizeof a, "%.6f", p.mean_depth[g]); snprintf(b, sizeof b, "%.6f", p.tin[g]);
+        f << gene_ids[g] << '\t' << gene_len[g] << '\t' << rows[g].covered << '\t' << rows[g].depth_sum << '\t' << rows[g].max_depth << '\t' << a << '\t' << b << NL;
+    }
+    f.close();
+    return f.good();
+}
+
+bool write_tin_summary(const std::string &path, const TinProfile &p) {
+    std::ofstream f(path);
+    char a[64], b[64], c[64];
+    snprintf(a, sizeof a, "%.6f", p.mean); snprintf(b, sizeof b, "%.6f", p.median); snprintf(c, sizeof c, "%.6f", p.stdev);
+    f << "genes\teligible\tmean\tmedian\tstdev" << NL << p.tin.size() << '\t' << p.eligible << '\t' << a << '\t' << b << '\t' << c << NL;
+    f.close();
+    return f.good();
+}
+
 }  // namespace rsqc_host

@@ -62,4 +62,22 @@ GeneBodyProfile gene_body_profile(const GeneBodyModel &model, const uint64_t *su
 // <output>/<sample>.gene_body.tsv: bin, depth_sum, genes, norm_mean -- 100 rows, bin 0 = the 5' end.  False: the file could not be written
 bool write_gene_body(const std::string &path, const GeneBodyProfile &profile);
 
+// --tin: the file's floating columns and the summary from the rows of rsqc_tin_rows (one per gene of the GeneBodyModel, whose
+// gene_len is L).  mean_depth = S / L (0 for L = 0).  A gene is eligible when L >= 100 and S >= L; for it, in doubles,
+// H = ln(S) - E ln(2) / S and tin = 100 exp(H) / L; every other gene has tin 0.  The summary covers the eligible genes' tin: mean
+// (summed in gene order), median (of the sorted values; the mean of the two middle ones for an even count) and the population
+// standard deviation; all three 0 without an eligible gene
+struct TinProfile {
+    std::vector<double> mean_depth, tin;
+    std::vector<uint8_t> is_eligible;
+    uint64_t eligible = 0;
+    double mean = 0, median = 0, stdev = 0;
+};
+TinProfile tin_profile(const uint32_t *gene_len, size_t n_genes, const rsqc_tin_row *rows);
+// <output>/<sample>.tin.tsv: gene_id, length, covered, depth_sum, max_depth, mean_depth, tin -- one row per listed gene, in the order
+// and with the ids of gene_reads.gct.  False: the file could not be written
+bool write_tin(const std::string &path, const std::vector<std::string> &gene_ids, const uint32_t *gene_len, const rsqc_tin_row *rows, const TinProfile &profile);
+// <output>/<sample>.tin_summary.tsv: genes, eligible, mean, median, stdev -- one row
+bool write_tin_summary(const std::string &path, const TinProfile &profile);
+
 }  // namespace rsqc_host

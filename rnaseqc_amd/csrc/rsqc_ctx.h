@@ -192,6 +192,17 @@ struct GenebodyState {
     uint64_t *h_sums = nullptr; size_t h_sums_cap = 0; // page-locked, in values: the window of the last rsqc_genebody_sums
 };
 
+// --tin (rsqc_tin_begin / rsqc_tin_end / rsqc_tin_rows, rsqc_tin_api.cpp): a model of its own (12 bytes per segment), the launch plan
+// (20 bytes per item, 8 per gene), one partial per item and one row per gene on the device (24 bytes each), the rows on the host
+struct TinState {
+    bool active = false, done = false;
+    int32_t n_genes = 0;
+    uint64_t n_items = 0;
+    DevBuf seg_tid, seg_start, seg_end, items, item_off, part, rows;
+    rsqc_tin_info info{};
+    rsqc_tin_row *h_rows = nullptr; size_t h_rows_cap = 0;   // page-locked, in rows: every gene's row behind rsqc_tin_end
+};
+
 }  // namespace rsqc
 using namespace rsqc;            // (every unit that sees this header is host code of the library)
 
@@ -287,6 +298,7 @@ struct rsqc_ctx {
     JunctionState junc;
     TrackState track;
     GenebodyState genebody;
+    TinState tin;
     MarkdupState markdup;
 
     // host results
@@ -334,6 +346,8 @@ int track_events(rsqc_ctx *c, const UploadedBatch *u, const DevBatch &d);
 void track_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forgets the track
 // --gene-body: the stage behind rsqc_track_end (rsqc_genebody_api.cpp)
 void genebody_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the model and the sums
+// --tin: the stage behind rsqc_track_end (rsqc_tin_api.cpp)
+void tin_drop(rsqc_ctx *c, bool free_buffers);        // ends the mode and forgets the model and the rows
 
 template <class T>
 int upload(rsqc_ctx *c, std::vector<DevBuf> &owner, const T *host, size_t n, const T **out, bool from_pool = false) {

@@ -91,6 +91,9 @@ def load_library():
         lib.rsqc_genebody_begin.argtypes = [vp, C.c_int32] + [vp] * 5
         lib.rsqc_genebody_end.argtypes = [vp, C.POINTER(abi.GenebodyInfo)]
         lib.rsqc_genebody_sums.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+        lib.rsqc_tin_begin.argtypes = [vp, C.c_int32] + [vp] * 4
+        lib.rsqc_tin_end.argtypes = [vp, C.POINTER(abi.TinInfo)]
+        lib.rsqc_tin_rows.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         _lib = lib
     return _lib
 
@@ -105,6 +108,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_sort_begin", "rsqc_sort_end", "rsqc_markdup_begin", "rsqc_markdup_end", "rsqc_markdup_verdicts", "rsqc_markdup_use_umi", "rsqc_markdup_umi_end", "rsqc_markdup_umi_edits", "rsqc_markdup_umi_group_end", "rsqc_umi_pack", "rsqc_junctions_begin", "rsqc_junctions_end",
     "rsqc_track_begin", "rsqc_track_end", "rsqc_track_rows", "rsqc_track_text",
     "rsqc_genebody_begin", "rsqc_genebody_end", "rsqc_genebody_sums",
+    "rsqc_tin_begin", "rsqc_tin_end", "rsqc_tin_rows",
 ]
 
 
@@ -385,6 +389,30 @@ class Engine:
         p = C.c_void_p()
         self._check(self._l.rsqc_genebody_sums(self._h, int(first_gene), int(n), C.byref(p)))
         return abi._view(p.value, int(n) * abi.GENEBODY_BINS, np.uint64).copy().reshape(int(n), abi.GENEBODY_BINS)
+
+    # ---- per-gene transcript integrity (rsqc_tin_*) -------------------------------------------------------------------
+    def tin_begin(self, seg_off, seg_tid, seg_start, seg_end):
+        """Behind track_begin and before the first submit: the model of the pass, as for genebody_begin without `reverse` (the
+        figures are symmetric in the strand)."""
+        off = np.ascontiguousarray(seg_off, dtype=np.uint32)
+        tid = np.ascontiguousarray(seg_tid, dtype=np.int32)
+        start, end = np.ascontiguousarray(seg_start, dtype=np.uint32), np.ascontiguousarray(seg_end, dtype=np.uint32)
+        assert len(off) >= 1 and len(tid) == len(start) == len(end)
+        self._check(self._l.rsqc_tin_begin(self._h, len(off) - 1, abi.ptr(off), abi.ptr(tid), abi.ptr(start), abi.ptr(end)))
+
+    def tin_end(self) -> dict:
+        """After track_end(): the rows are built on the device and copied to the host; the fields of rsqc_tin_info."""
+        info = abi.TinInfo()
+        self._check(self._l.rsqc_tin_end(self._h, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in abi.TinInfo._fields_}
+
+    def tin_rows(self, first_gene, n) -> np.ndarray:
+        """The rows of genes [first_gene, first_gene + n) as a structured array of abi.TIN_ROW (a copy)."""
+        p = C.c_void_p()
+        self._check(self._l.rsqc_tin_rows(self._h, int(first_gene), int(n), C.byref(p)))
+        if not int(n):
+            return np.zeros(0, abi.TIN_ROW)
+        return abi._view(p.value, int(n) * abi.TIN_ROW.itemsize, np.uint8).copy().view(abi.TIN_ROW)
 
     def read_device(self, ptr, count, dtype):
         """count items of dtype from a device pointer of this context (tests): hipMemcpy of the HIP runtime the library itself is

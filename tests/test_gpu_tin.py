@@ -1,0 +1,193 @@
+"""-m gpu: --tin through the C ABI (rsqc_tin_begin / rsqc_tin_end / rsqc_tin_rows, rnaseqc_amd/csrc/rsqc_tin.hip).  The edge catalogue
+of tests/tin_cases.py in one batch, in many small batches, with the later track events merged and lane by lane, and under
+rsqc_sort_begin on shuffled records: the integers and figures are compared, bit for bit, with the restatement of the contract
+(tests/tin_ref.py), the double within the contract's bound, and its bits are the same in all four modes."""
+import numpy as np
+import pytest
+
+from rnaseqc_amd import abi, engine
+from rnaseqc_amd.model import Annotation
+from tests import genebody_cases as gc
+from tests import genebody_ref as gref
+from tests import junction_cases as jc
+from tests import tin_cases as tc
+from tests import tin_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+# an annotation the records of the catalogue do not touch: the per-read kernels see intergenic reads (this file is about the track)
+ANN_ROWS = [dict(contig="c2", type="gene", start=2900, end=2999, strand="+", gene_id="g"), dict(contig="c2", type="exon", start=2900, end=2999, strand="+", gene_id="g")]
+MODES = ["one_batch", "many_batches_lane_by_lane", "many_batches_merged", "shuffled_under_sort"]
+
+
+@pytest.fixture(scope="module")
+def one():
+    """One context, reset between the passes."""
+    e = engine.Engine(abi.default_params())
+    e.set_annotation(Annotation.from_rows(["c0", "c1", "c2"], ANN_ROWS))
+    yield e
+    e.close()
+
+
+def _batches(batches, mode):
+    if mode == "one_batch" or not batches:
+        return batches
+    b = batches[0]
+    if mode == "shuffled_under_sort":
+        b = b.take(np.random.default_rng(77).permutation(b.n))
+    cuts = jc.unequal_cuts(b.n, 11, min(7, b.n))
+    return [b.slice(lo, hi) for lo, hi in zip(cuts[:-1], cuts[1:])]
+
+
+def _pass(e, lengths, batches, model, sort=False, window=None, genebody=None, tin=True):
+    e.reset()
+    if sort:
+        e.sort_begin()
+    e.track_begin(lengths)
+    if genebody is not None and genebody[0] == "first":
+        e.genebody_begin(**genebody[1])
+    if tin:
+        e.tin_begin(**model)
+    if genebody is not None and genebody[0] == "second":
+        e.genebody_begin(**genebody[1])
+    for b in batches:
+        e.submit(b)
+    if sort:
+        e.sort_end()
+    e.finalize()
+    e.track_end()
+    body = None
+    if genebody is not None:
+        gi = e.genebody_end()
+        body = (e.genebody_sums(0, gi["n_genes"]), gi)
+    if not tin:
+        return None, None, body
+    info = e.tin_end()
+    n = len(model["seg_off"]) - 1
+    step = window or max(n, 1)
+    parts = [e.tin_rows(k, min(step, n - k)) for k in range(0, n, step)]
+    return (np.concatenate(parts) if parts else np.zeros(0, ref.ROW)), info, body
+
+
+def _run_case(e, name, mode, monkeypatch):
+    lengths, batches, model, _, want, want_info, L = tc.case(name)
+    monkeypatch.setenv("RSQC_TRACK_MERGE", "0" if mode == "many_batches_lane_by_lane" else "1")
+    got, info, _ = _pass(e, lengths, _batches(batches, mode), model, sort=mode == "shuffled_under_sort", window=3 if mode == "many_batches_merged" else None)
+    assert got.dtype == ref.ROW
+    ref.assert_rows(got, info, want, want_info, L)
+    assert (info["tin_ms"] > 0) == (want_info["n_genes"] > 0)              # (no gene: no launch)
+    return got, info
+
+
+@pytest.mark.parametrize("name", tc.SMALL)
+def test_catalogue(one, name, monkeypatch):
+    """The four modes in one test: each against the reference, and the bits of every row equal between them."""
+    first = None
+    for mode in MODES:
+        got, info = _run_case(one, name, mode, monkeypatch)
+        if first is None:
+            first = got
+        assert got.tobytes() == first.tobytes(), (name, mode)
+
+
+def test_70000_genes_of_one_base(one, monkeypatch):
+    a, _ = _run_case(one, "many_genes_of_one_base", "one_batch", monkeypatch)
+    b, _ = _run_case(one, "many_genes_of_one_base", "many_batches_lane_by_lane", monkeypatch)
+    assert a.tobytes() == b.tobytes()
+
+
+def test_sum_above_2_pow_32(one, monkeypatch):
+    """70 000 records 70000M over one gene of 70 000 bases: S = 4.9e9, 18 items added in item order."""
+    a, _ = _run_case(one, "sum_above_2_pow_32", "one_batch", monkeypatch)
+    b, _ = _run_case(one, "sum_above_2_pow_32", "many_batches_merged", monkeypatch)
+    assert a.tobytes() == b.tobytes() and int(a["depth_sum"][0]) == tc.BIG_RECORDS * tc.BIG_L > 1 << 32 and int(a["max_depth"][0]) == tc.BIG_RECORDS
+
+
+@pytest.mark.parametrize("order", ["first", "second"])
+def test_with_gene_body_in_one_pass(one, order, monkeypatch):
+    """rsqc_genebody_begin in front of or behind rsqc_tin_begin, each with a model of its own: the gene-body sums and info are those of
+    a pass without tin, the tin rows those of a pass without gene-body."""
+    monkeypatch.setenv("RSQC_TRACK_MERGE", "1")
+    e = one
+    lengths, batches, model, _, want, want_info, L = tc.case("item_edges")
+    _, _, body_model, _, body_want, body_info = gc.case("same_reads_forward_and_reverse")       # (the same records: gc._everywhere())
+    alone, alone_info, _ = _pass(e, lengths, batches, model)
+    _, _, body_alone = _pass(e, lengths, batches, model, genebody=(order, body_model), tin=False)
+    both, both_info, body_both = _pass(e, lengths, batches, model, genebody=(order, body_model))
+    ref.assert_rows(both, both_info, want, want_info, L)
+    assert both.tobytes() == alone.tobytes() and {f: both_info[f] for f in ref.INFO} == {f: alone_info[f] for f in ref.INFO}
+    gref.assert_equal(body_both[0], body_both[1], body_want, body_info)
+    assert (body_both[0] == body_alone[0]).all() and {f: body_both[1][f] for f in gref.INFO} == {f: body_alone[1][f] for f in gref.INFO}
+
+
+def test_second_end_windows_reset_and_a_new_pass(one, monkeypatch):
+    """A second rsqc_tin_end returns the same figures (the event time included: no device work); windows; after rsqc_reset the context
+    takes another model over another track; a pass without the calls refuses rsqc_tin_end."""
+    e = one
+    got, info = _run_case(e, "item_edges", "one_batch", monkeypatch)
+    assert e.tin_end() == info
+    assert e.tin_rows(0, len(got)).tobytes() == got.tobytes() and e.tin_rows(3, 1).tobytes() == got[3:4].tobytes() and e.tin_rows(len(got), 0).shape == (0,)
+    for first, n in ((len(got) - 1, 2), (len(got) + 1, 0), (0, len(got) + 1)):
+        with pytest.raises(engine.EngineError) as err:
+            e.tin_rows(first, n)
+        assert err.value.code == abi.ERR_ARG
+    _run_case(e, "contig_starts_and_ends", "one_batch", monkeypatch)
+    _run_case(e, "sum_above_2_pow_32", "one_batch", monkeypatch)           # another track
+    _run_case(e, "item_edges", "many_batches_merged", monkeypatch)
+    e.reset()                                                              # a pass without the calls behind one with them: the mode has ended
+    e.track_begin(tc.LENGTHS)
+    e.finalize()
+    e.track_end()
+    with pytest.raises(engine.EngineError) as err:
+        e.tin_end()
+    assert err.value.code == abi.ERR_ARG and "rsqc_tin_begin must precede" in str(err.value)
+
+
+@pytest.mark.parametrize("name", list(tc.BROKEN))
+def test_every_model_rule_violated_once(one, name):
+    model, word, gene = tc.broken_model(name)
+    e = one
+    e.reset()
+    e.track_begin(tc.LENGTHS)
+    with pytest.raises(engine.EngineError) as err:
+        e.tin_begin(**model)
+    assert err.value.code == abi.ERR_ARG and "rsqc_tin_begin" in str(err.value) and word in str(err.value) and gene in str(err.value), str(err.value)
+    _, _, good, _, _, _, _ = tc.case("no_records")                         # the refusal leaves the pass usable
+    e.tin_begin(**good)
+    e.finalize()
+    e.track_end()
+    assert e.tin_end()["n_measured"] == 2
+
+
+def test_call_order():
+    def refused(call, text, code=abi.ERR_ARG):
+        with pytest.raises(engine.EngineError) as err:
+            call()
+        assert err.value.code == code and text in str(err.value), str(err.value)
+
+    lengths, batches, model, _, want, want_info, L = tc.case("lengths_1_63_64_65_99_100")
+    begin = lambda: e.tin_begin(**model)
+    e = engine.Engine(abi.default_params())
+    try:
+        e.set_annotation(Annotation.from_rows(["c0", "c1", "c2"], ANN_ROWS))
+        refused(begin, "rsqc_track_begin")                                 # no track
+        refused(e.tin_end, "rsqc_tin_begin must precede")
+        e.track_begin(lengths)
+        e.submit(batches[0])
+        refused(begin, "first submit")                                     # behind a submit of the same pass
+        e.reset()
+        refused(begin, "rsqc_track_begin")                                 # the track of the pass before does not count
+        e.track_begin(lengths)
+        begin()
+        refused(begin, "already")                                          # twice
+        e.submit(batches[0])
+        refused(e.tin_end, "rsqc_track_end must precede")                  # the pass is not finalized, the track not ended
+        refused(lambda: e.tin_rows(0, 1), "rsqc_tin_end must precede")
+        e.finalize()
+        refused(e.tin_end, "rsqc_track_end must precede")
+        e.track_end()
+        refused(begin, "rsqc_track_begin")                                 # behind rsqc_track_end
+        info = e.tin_end()
+        ref.assert_rows(e.tin_rows(0, 6), info, want, want_info, L)
+    finally:
+        e.close()
