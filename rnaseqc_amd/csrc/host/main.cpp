@@ -700,8 +700,15 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     if (!shares_contigs(S, ann, bam_contigs)) { cerr << S.prefix << "BAM file shares no contigs with GTF" << endl; return 11; }
     if (o.bedgraph || o.gene_body || o.tin)            // the track needs every contig's length
         for (size_t k = 0; k < bam_contigs.size(); ++k)
-            if (k >= in.lengths.size() || in.lengths[k] == 0) { cerr << S.prefix << (o.tin ? o.bedgraph ? o.gene_body ? "--bedgraph, --gene-body and --tin need" : "--bedgraph and --tin need" : o.gene_body ? "--gene-body and --tin need" : "--tin needs"
-                                                                                      : o.bedgraph ? o.gene_body ? "--bedgraph and --gene-body need" : "--bedgraph needs" : "--gene-body needs") << " the length (LN) of every contig in the header: none for " << bam_contigs[k] << endl; return 10; }
+            if (k >= in.lengths.size() || in.lengths[k] == 0) {
+                std::vector<const char *> flags;       // "--a needs", "--a and --b need", "--a, --b and --c need"
+                if (o.bedgraph) flags.push_back("--bedgraph");
+                if (o.gene_body) flags.push_back("--gene-body");
+                if (o.tin) flags.push_back("--tin");
+                std::string who;
+                for (size_t f = 0; f < flags.size(); ++f) who += std::string(f == 0 ? "" : f + 1 == flags.size() ? " and " : ", ") + flags[f];
+                cerr << S.prefix << who << (flags.size() > 1 ? " need" : " needs") << " the length (LN) of every contig in the header: none for " << bam_contigs[k] << endl; return 10;
+            }
     const bool same_header = S.flattened && bam_contigs == S.contigs;
     if (!same_header) flatten_for(S, ann, bam_contigs);
     // --gene-body, --tin: the model of this header's contigs and lengths (one for both), built when either changes
@@ -719,10 +726,11 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     rsqc_ctx *gpu = S.gpu;
     int rc;
     auto hip_failed = [&](int code) { if (code == RSQC_ERR_HIP) row.fatal = true; return code; };
+    auto gpu_failed = [&](int code) { cerr << S.prefix << rsqc_strerror(code) << ": " << rsqc_last_error(gpu) << endl; hip_failed(code); return 10; };      // a call of the library that failed: its text, exit 10
     if (S.dirty || (S.inputs_set && !same_header)) {
         // another contig order, or a sample that failed in the middle of its pass: everything in flight is waited for and the
         // context is as rsqc_create left it (its streams, pools and decode buffers kept)
-        if ((rc = rsqc_clear_inputs(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+        if ((rc = rsqc_clear_inputs(gpu)) != RSQC_OK) return gpu_failed(rc);
         S.inputs_set = false; S.dirty = false; S.needs_reset = false;
     }
     if (!S.inputs_set) {
@@ -731,7 +739,7 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (o.has_fasta) if (int code = set_reference(S, ann, {gpu}, rc)) { hip_failed(rc); return code; }
         S.inputs_set = true; S.dirty = false;
     } else if (S.needs_reset) {
-        if ((rc = rsqc_reset(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+        if ((rc = rsqc_reset(gpu)) != RSQC_OK) return gpu_failed(rc);
     }
     S.needs_reset = false;
 
@@ -808,33 +816,29 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     S.t_loop0 = Clock::now();
     rc = RSQC_OK;
     // --sort: the loops below collect (no per-read kernel runs); rsqc_sort_end orders the records and runs them
-    if (o.sort && (rc = rsqc_sort_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    if (o.sort && (rc = rsqc_sort_begin(gpu)) != RSQC_OK) return gpu_failed(rc);
     // --mark-duplicates: rsqc_sort_end first rewrites flag 0x400 of the collection
-    if (o.mark_duplicates && (rc = rsqc_markdup_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    if (o.mark_duplicates && (rc = rsqc_markdup_begin(gpu)) != RSQC_OK) return gpu_failed(rc);
     // --umi-tag / --umi-qname: the UMI key of the decode streams / the host reader's batches joins the signature
-    if ((o.has_umi_tag || o.has_umi_qname) && (rc = rsqc_markdup_use_umi(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
-    if (o.umi_edits == "1" && (rc = rsqc_markdup_umi_edits(gpu, 1)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    if ((o.has_umi_tag || o.has_umi_qname) && (rc = rsqc_markdup_use_umi(gpu)) != RSQC_OK) return gpu_failed(rc);
+    if (o.umi_edits == "1" && (rc = rsqc_markdup_umi_edits(gpu, 1)) != RSQC_OK) return gpu_failed(rc);
     // --junctions: every batch the per-read kernels run leaves its junction instances on the device (under --sort: the sorted batches)
-    if (o.junctions && (rc = rsqc_junctions_begin(gpu)) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    if (o.junctions && (rc = rsqc_junctions_begin(gpu)) != RSQC_OK) return gpu_failed(rc);
     // --bedgraph: and its coverage events, in a difference array over the header's contigs (kept by the context while it is large enough)
     if (o.bedgraph || o.gene_body || o.tin) {
         std::vector<const char *> track_names;
         for (auto &nm : bam_contigs) track_names.push_back(nm.c_str());
-        if ((rc = rsqc_track_begin(gpu, n_ref_bam, in.lengths.data(), track_names.data())) != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+        if ((rc = rsqc_track_begin(gpu, n_ref_bam, in.lengths.data(), track_names.data())) != RSQC_OK) return gpu_failed(rc);
     }
     // --gene-body: the model of this header's contigs (built when the header changes), checked, planned and uploaded
     if (o.gene_body) {
         const GeneBodyModel &m = S.gene_body;
-        if ((rc = rsqc_genebody_begin(gpu, (int32_t)m.reverse.size(), m.seg_off.data(), m.seg_tid.data(), m.seg_start.data(), m.seg_end.data(), m.reverse.data())) != RSQC_OK) {
-            cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10;
-        }
+        if ((rc = rsqc_genebody_begin(gpu, (int32_t)m.reverse.size(), m.seg_off.data(), m.seg_tid.data(), m.seg_start.data(), m.seg_end.data(), m.reverse.data())) != RSQC_OK) return gpu_failed(rc);
     }
     // --tin: the same model without its strands, in buffers of the mode's own
     if (o.tin) {
         const GeneBodyModel &m = S.gene_body;
-        if ((rc = rsqc_tin_begin(gpu, (int32_t)m.gene_len.size(), m.seg_off.data(), m.seg_tid.data(), m.seg_start.data(), m.seg_end.data())) != RSQC_OK) {
-            cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10;
-        }
+        if ((rc = rsqc_tin_begin(gpu, (int32_t)m.gene_len.size(), m.seg_off.data(), m.seg_tid.data(), m.seg_start.data(), m.seg_end.data())) != RSQC_OK) return gpu_failed(rc);
     }
     if (sam_input) {
         // ---- SAM text: the host reads the file (plain) or frames its BGZF blocks, the device does the rest
@@ -960,7 +964,7 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     }
     if (rc == RSQC_ERR_BAD_CIGAR) throw std::invalid_argument("Unrecognized Cigar Op ");
     if (rc == RSQC_ERR_EMPTY_MEDIAN) throw std::range_error("Cannot compute median of an empty list");
-    if (rc != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+    if (rc != RSQC_OK) return gpu_failed(rc);
     S.dirty = false; S.needs_reset = true;
     if (o.verbosity) {
         const double secs = seconds_between(S.t_loop0, S.t_loop1);
@@ -994,7 +998,7 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         // the track's text comes from the context window by window: written here, on the report path, before the context's next reset
         uint64_t bytes = 0; double secs = 0; bool io_failed = false;
         rc = write_bedgraph(gpu, out_dir + "/" + sample.name + ".coverage.bedgraph", track.n_rows, bytes, secs, io_failed);
-        if (rc != RSQC_OK) { cerr << S.prefix << rsqc_strerror(rc) << ": " << rsqc_last_error(gpu) << endl; hip_failed(rc); return 10; }
+        if (rc != RSQC_OK) return gpu_failed(rc);
         if (io_failed) { cerr << S.prefix << "Filesystem error:  cannot write " << out_dir << "/" << sample.name << ".coverage.bedgraph" << endl; return 8; }
         if (o.verbosity) cout << "Track text: rows " << track.n_rows << ", bytes " << bytes << ", seconds " << secs << endl;
     }

@@ -24,6 +24,20 @@ int dev_alloc(rsqc_ctx *c, DevBuf &b, size_t bytes, bool zero) {
     if (zero) HIP_TRY(c, hipMemsetAsync(b.p, 0, b.bytes, c->stream));
     return 0;
 }
+bool dev_reserve(DevBuf &b, size_t bytes) {
+    if (b.bytes >= bytes) return true;
+    b.release();
+    if (hipMalloc(&b.p, bytes) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
+    b.bytes = bytes;
+    return true;
+}
+bool host_reserve(HostBuf &b, size_t bytes) {
+    if (b.bytes >= bytes) return true;
+    b.release();
+    if (hipHostMalloc(&b.p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
+    b.bytes = bytes;
+    return true;
+}
 
 static int zero_accumulators(rsqc_ctx *c) {
     // one zeroing kernel + one store (rl_stats[1] = min l_qseq starts at UINT_MAX) instead of several memsets

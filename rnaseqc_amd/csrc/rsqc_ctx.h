@@ -40,6 +40,10 @@ struct DevBuf {
     void *p = nullptr; size_t bytes = 0;
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
+struct HostBuf {                   // page-locked host memory: a window of results that grows only (host_reserve)
+    void *p = nullptr; size_t bytes = 0;
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; bytes = 0; }
+};
 struct UploadedBatch {
     DevBatch d{};
     std::vector<DevBuf> bufs;
@@ -178,29 +182,32 @@ struct TrackState {
     rsqc_track_info info{};
     std::vector<int32_t> h_tid;                        // the window of the last rsqc_track_rows
     std::vector<uint32_t> h_start, h_end, h_depth;
-    char *h_text = nullptr; size_t h_text_cap = 0;     // page-locked: the window of the last rsqc_track_text
+    HostBuf h_text;                                    // the window of the last rsqc_track_text
 };
 
-// --gene-body (rsqc_genebody_begin / rsqc_genebody_end / rsqc_genebody_sums, rsqc_genebody_api.cpp): the model (12 bytes per
-// segment) and the launch plan (24 bytes per item) of the pass, the sums on the device (800 bytes per gene), one window on the host
-struct GenebodyState {
+// What the stages over the track that follow a gene model hold alike (rsqc_genemodel_api.cpp): the model of the pass (12 bytes per
+// segment) and the items of its launch plan, each stage its own
+struct GeneStage {
     bool active = false, done = false;
     int32_t n_genes = 0;
     uint64_t n_items = 0;
-    DevBuf seg_tid, seg_start, seg_end, items, sums, total;
+    DevBuf seg_tid, seg_start, seg_end, items;
+};
+
+// --gene-body (rsqc_genebody_begin / rsqc_genebody_end / rsqc_genebody_sums, rsqc_genebody_api.cpp): 24 bytes per item, the sums on
+// the device (800 bytes per gene), one window on the host
+struct GenebodyState : GeneStage {
+    DevBuf sums, total;
     rsqc_genebody_info info{};
-    uint64_t *h_sums = nullptr; size_t h_sums_cap = 0; // page-locked, in values: the window of the last rsqc_genebody_sums
+    HostBuf h_sums;                                    // the window of the last rsqc_genebody_sums
 };
 
-// --tin (rsqc_tin_begin / rsqc_tin_end / rsqc_tin_rows, rsqc_tin_api.cpp): a model of its own (12 bytes per segment), the launch plan
-// (20 bytes per item, 8 per gene), one partial per item and one row per gene on the device (24 bytes each), the rows on the host
-struct TinState {
-    bool active = false, done = false;
-    int32_t n_genes = 0;
-    uint64_t n_items = 0;
-    DevBuf seg_tid, seg_start, seg_end, items, item_off, part, rows;
+// --tin (rsqc_tin_begin / rsqc_tin_end / rsqc_tin_rows, rsqc_tin_api.cpp): 20 bytes per item, 8 per gene, one partial per item and
+// one row per gene on the device (24 bytes each), the rows on the host
+struct TinState : GeneStage {
+    DevBuf item_off, part, rows;
     rsqc_tin_info info{};
-    rsqc_tin_row *h_rows = nullptr; size_t h_rows_cap = 0;   // page-locked, in rows: every gene's row behind rsqc_tin_end
+    HostBuf h_rows;                                    // every gene's row behind rsqc_tin_end
 };
 
 }  // namespace rsqc
@@ -318,6 +325,10 @@ namespace rsqc {
 
 int fail(rsqc_ctx *c, int code, const std::string &msg);
 int dev_alloc(rsqc_ctx *c, DevBuf &b, size_t bytes, bool zero);
+// a buffer of at least `bytes` that grows only (its content is lost when it grows).  false: there is no such memory -- the HIP error
+// is cleared and the buffer is empty; the caller composes the text
+bool dev_reserve(DevBuf &b, size_t bytes);
+bool host_reserve(HostBuf &b, size_t bytes);
 hipEvent_t get_event(rsqc_ctx *c);
 int resolve_events(rsqc_ctx *c);
 // device buffer of at least `bytes` from the context's pool of retired upload buffers (smallest that fits), or empty
@@ -348,6 +359,33 @@ void track_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forge
 void genebody_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the model and the sums
 // --tin: the stage behind rsqc_track_end (rsqc_tin_api.cpp)
 void tin_drop(rsqc_ctx *c, bool free_buffers);        // ends the mode and forgets the model and the rows
+// what the two have in common (rsqc_genemodel_api.cpp).  who: the public call, for the texts; what: the stage, as the texts name it.
+// A begin behind its own argument checks (the order of the calls, the model against the track's contigs; n_seg: its segments), the
+// figures its capacity texts end with, the model and the items reserved and copied (stream order: the caller synchronises); an end
+// (the order of the calls, then `run` once a pass: a run that fails leaves the pass void until rsqc_reset)
+int gene_begin_check(rsqc_ctx *c, const char *who, const char *what, const GeneStage &G, int32_t n_genes, const uint32_t *seg_off, const int32_t *seg_tid,
+                     const uint32_t *seg_start, const uint32_t *seg_end, size_t *n_seg);
+std::string gene_sizes(int32_t n_genes, size_t n_seg, size_t n_items);
+int gene_reserve(rsqc_ctx *c, const char *who, DevBuf &b, size_t bytes, const char *what, const std::string &sizes);
+int gene_upload(rsqc_ctx *c, const char *who, GeneStage &G, const std::string &sizes, int32_t n_genes, size_t n_seg, const int32_t *seg_tid,
+                const uint32_t *seg_start, const uint32_t *seg_end, const void *items, size_t n_items, size_t item_bytes);
+void gene_drop(GeneStage &G, bool free_buffers);
+int gene_end(rsqc_ctx *c, GeneStage &G, const char *begin, const char *end, int (*run)(rsqc_ctx *));
+// `work` enqueued between a pair of events and `after` behind it (the copies of what it left), the stream synchronised: its milliseconds
+template <class Work, class After>
+int run_timed(rsqc_ctx *c, double *ms, Work work, After after) {
+    hipEvent_t e0 = get_event(c), e1 = get_event(c);
+    HIP_TRY(c, hipEventRecord(e0, c->stream));
+    work();
+    HIP_TRY(c, hipEventRecord(e1, c->stream));
+    if (int rc = after()) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    float f = 0.f;
+    *ms = hipEventElapsedTime(&f, e0, e1) == hipSuccess ? f : 0;
+    c->event_pool.push_back(e0); c->event_pool.push_back(e1);
+    return 0;
+}
 
 template <class T>
 int upload(rsqc_ctx *c, std::vector<DevBuf> &owner, const T *host, size_t n, const T **out, bool from_pool = false) {

@@ -10,14 +10,8 @@ namespace {
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 int alloc_or_capacity(rsqc_ctx *c, DevBuf &b, size_t bytes, const char *what) {
-    if (b.bytes >= bytes) return 0;
-    b.release();
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        (void)hipGetLastError(); b.p = nullptr;
-        return fail(c, RSQC_ERR_CAPACITY, std::string("rsqc_junctions_end: no device memory for ") + what + " (" + std::to_string(bytes >> 20) + " MiB)");
-    }
-    b.bytes = bytes;
-    return 0;
+    if (dev_reserve(b, bytes)) return 0;
+    return fail(c, RSQC_ERR_CAPACITY, std::string("rsqc_junctions_end: no device memory for ") + what + " (" + std::to_string(bytes >> 20) + " MiB)");
 }
 
 // the collection's three columns with room for `need` instances, grown by doubling like the columns of --sort: new columns, a

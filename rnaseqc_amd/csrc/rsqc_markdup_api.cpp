@@ -10,18 +10,12 @@ namespace {
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 int alloc_or_capacity(rsqc_ctx *c, DevBuf &b, size_t bytes, const char *what, uint64_t anchors) {
-    if (b.bytes >= bytes) return 0;
-    b.release();
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        (void)hipGetLastError(); b.p = nullptr;
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        return fail(c, RSQC_ERR_CAPACITY, std::string("rsqc_sort_end: no device memory for ") + what + " of the duplicate marking (" + std::to_string(bytes >> 20) + " MiB; " +
-                                              std::to_string(c->sort.n) + " records collected, " + std::to_string(anchors) + " anchors, " + std::to_string(free_b >> 20) + " MiB of " +
-                                              std::to_string(total_b >> 20) + " MiB free)");
-    }
-    b.bytes = bytes;
-    return 0;
+    if (dev_reserve(b, bytes)) return 0;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    return fail(c, RSQC_ERR_CAPACITY, std::string("rsqc_sort_end: no device memory for ") + what + " of the duplicate marking (" + std::to_string(bytes >> 20) + " MiB; " +
+                                          std::to_string(c->sort.n) + " records collected, " + std::to_string(anchors) + " anchors, " + std::to_string(free_b >> 20) + " MiB of " +
+                                          std::to_string(total_b >> 20) + " MiB free)");
 }
 
 // scratch of the stage: released before markdup_run returns, so before the coordinate sort allocates

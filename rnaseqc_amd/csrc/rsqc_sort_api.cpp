@@ -46,14 +46,8 @@ int grow_columns(rsqc_ctx *c, DevBuf *const *cols, const size_t *width, int n_co
 }
 
 int alloc_or_capacity(rsqc_ctx *c, DevBuf &b, size_t bytes, const char *what) {
-    if (b.bytes >= bytes) return 0;
-    b.release();
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        (void)hipGetLastError(); b.p = nullptr;
-        return fail(c, RSQC_ERR_CAPACITY, std::string("rsqc_sort_end: no device memory for ") + what + " (" + std::to_string(bytes >> 20) + " MiB, " + std::to_string(c->sort.n) + " records collected)");
-    }
-    b.bytes = bytes;
-    return 0;
+    if (dev_reserve(b, bytes)) return 0;
+    return fail(c, RSQC_ERR_CAPACITY, std::string("rsqc_sort_end: no device memory for ") + what + " (" + std::to_string(bytes >> 20) + " MiB, " + std::to_string(c->sort.n) + " records collected)");
 }
 
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }

@@ -4,7 +4,7 @@
 
 namespace rsqc {
 
-void launch_tin_items(hipStream_t s, const uint32_t *S, const uint64_t *off, const TinModel &M, const TinItem *items, uint64_t n_items, rsqc_tin_row *part) {
+void launch_tin_items(hipStream_t s, const uint32_t *S, const uint64_t *off, const GeneModel &M, const TinItem *items, uint64_t n_items, rsqc_tin_row *part) {
     if (!n_items) return;
     const uint32_t grid = (uint32_t)((n_items + RSQC_TIN_WAVES - 1) / RSQC_TIN_WAVES);
     tin_items_kernel<<<grid, RSQC_TIN_THREADS, 0, s>>>(S, off, M, items, n_items, part);

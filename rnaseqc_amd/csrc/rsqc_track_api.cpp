@@ -11,14 +11,8 @@ namespace {
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 int alloc_or_capacity(rsqc_ctx *c, DevBuf &b, size_t bytes, const char *who, const char *what) {
-    if (b.bytes >= bytes) return 0;
-    b.release();
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        (void)hipGetLastError(); b.p = nullptr;
-        return fail(c, RSQC_ERR_CAPACITY, std::string(who) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)");
-    }
-    b.bytes = bytes;
-    return 0;
+    if (dev_reserve(b, bytes)) return 0;
+    return fail(c, RSQC_ERR_CAPACITY, std::string(who) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)");
 }
 
 TrackRows rows_of(const TrackState &T) {
@@ -100,8 +94,7 @@ void track_drop(rsqc_ctx *c, bool free_buffers) {
     T.h_tid.clear(); T.h_start.clear(); T.h_end.clear(); T.h_depth.clear();
     if (free_buffers) {
         for (DevBuf *b : {&T.diff, &T.off, &T.length, &T.sums, &T.names, &T.name_off, &T.counts, &T.chunk_sum, &T.totals, &T.rows, &T.linelen, &T.text}) b->release();
-        if (T.h_text) (void)hipHostFree(T.h_text);
-        T.h_text = nullptr; T.h_text_cap = 0;
+        T.h_text.release();
     }
 }
 
@@ -221,7 +214,7 @@ int rsqc_track_text(rsqc_ctx *c, uint64_t first, uint64_t n, const char **text, 
     TrackState &T = c->track;
     if (!T.have_names) return fail(c, RSQC_ERR_ARG, "rsqc_track_text: rsqc_track_begin was given no contig names");
     if (n > RSQC_TRACK_WINDOW) return fail(c, RSQC_ERR_ARG, "rsqc_track_text: " + std::to_string(n) + " rows in one call (at most 4194304)");
-    *text = T.h_text ? T.h_text : ""; *bytes = 0;
+    *text = T.h_text.p ? (const char *)T.h_text.p : ""; *bytes = 0;
     if (!n) return RSQC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
@@ -236,20 +229,14 @@ int rsqc_track_text(rsqc_ctx *c, uint64_t first, uint64_t n, const char **text, 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     if ((rc = alloc_or_capacity(c, T.text, (size_t)total + 64, "rsqc_track_text", "the text of a window"))) return rc;
-    if (T.h_text_cap < total) {
-        if (T.h_text) (void)hipHostFree(T.h_text);
-        T.h_text = nullptr; T.h_text_cap = 0;
+    if (T.h_text.bytes < total) {
         const size_t cap = std::max<size_t>((size_t)total + (size_t)total / 4, 1u << 20);
-        if (hipHostMalloc((void **)&T.h_text, cap, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); T.h_text = nullptr;
-            return fail(c, RSQC_ERR_CAPACITY, "rsqc_track_text: no page-locked memory for a window of " + std::to_string(cap) + " bytes");
-        }
-        T.h_text_cap = cap;
+        if (!host_reserve(T.h_text, cap)) return fail(c, RSQC_ERR_CAPACITY, "rsqc_track_text: no page-locked memory for a window of " + std::to_string(cap) + " bytes");
     }
     launch_track_format(c->stream, R, first, (uint32_t)n, (const uint32_t *)T.name_off.p, (const char *)T.names.p, (const uint32_t *)T.linelen.p, (char *)T.text.p);
-    HIP_TRY(c, hipMemcpyAsync(T.h_text, T.text.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(T.h_text.p, T.text.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    *text = T.h_text; *bytes = total;
+    *text = (const char *)T.h_text.p; *bytes = total;
     return RSQC_OK;
 }

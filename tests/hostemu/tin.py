@@ -1,5 +1,5 @@
-"""TEST HARNESS: the kernels and the launch plan of --tin (rnaseqc_amd/csrc/rsqc_tin.h) with the model check of rsqc_genebody.h on the
-64-lane fiber emulation (see tin_emu.cpp)."""
+"""TEST HARNESS: the kernels and the launch plan of --tin (rnaseqc_amd/csrc/rsqc_tin.h) with the model check and the walk of
+rsqc_genemodel.h on the 64-lane fiber emulation (see tin_emu.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -21,7 +21,8 @@ class ModelError(Exception):
 
 def build():
     csrc = os.path.join(_ROOT, "rnaseqc_amd", "csrc")
-    srcs = [PROGRAM_SOURCE, os.path.join(_HERE, "wavemu.h"), os.path.join(csrc, "rsqc_tin.h"), os.path.join(csrc, "rsqc_genebody.h"), os.path.join(_ROOT, "include", "rnaseqc_amd.h")]
+    srcs = [PROGRAM_SOURCE, os.path.join(_HERE, "wavemu.h"), os.path.join(_HERE, "genemodel_emu.h"), os.path.join(csrc, "rsqc_tin.h"), os.path.join(csrc, "rsqc_genemodel.h"),
+            os.path.join(_ROOT, "include", "rnaseqc_amd.h")]
     if not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-unused-function", "-Wno-unused-variable", srcs[0], "-o", _SO])
     return _SO

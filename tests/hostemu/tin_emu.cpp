@@ -1,27 +1,20 @@
 // tin_emu.cpp -- TEST HARNESS ONLY (never loaded by the product).
 //
-// The KERNELS of --tin -- rnaseqc_amd/csrc/rsqc_tin.h, unmodified, with the launch plan of the same header and the model check of
-// rsqc_genebody.h -- compiled for the host on top of the 64-lane fiber emulation of wavemu.h.  The host side of rsqc_tin_api.cpp (the
-// layout of the scanned difference array, the order of the steps) is restated here with plain memory: the depth of every position is
-// handed in, laid out as rsqc_track_end leaves it (contig t at off[t], one pad slot behind every contig, the depth of slot i at
-// i + 1).  The item slots and the rows start as a pattern that no kernel writes: a slot or row that is left out shows.  The expected
-// rows are NOT computed here: tests/tin_ref.py restates the contract in Python and the test compares.
+// The KERNELS of --tin -- rnaseqc_amd/csrc/rsqc_tin.h, unmodified, with the launch plan of the same header and the model check and
+// the walk of rsqc_genemodel.h -- compiled for the host on top of the 64-lane fiber emulation of wavemu.h.  The host side of
+// rsqc_tin_api.cpp (the layout of the scanned difference array, the order of the steps) is restated with plain memory: the depth of
+// every position is handed in and laid out as rsqc_track_end leaves it (genemodel_emu.h, shared with genebody_emu.cpp).  The item
+// slots and the rows start as a pattern that no kernel writes: a slot or row that is left out shows.  The expected rows are NOT
+// computed here: tests/tin_ref.py restates the contract in Python and the test compares.
 // With -DTINEMU_MAIN the file is a stand-alone program over a case file (for a sanitizer build).
 #include "wavemu.h"
 
-#include <string>
-#include <vector>
-
-#include "../../rnaseqc_amd/csrc/rsqc_genebody.h"
+#include "genemodel_emu.h"
 #include "../../rnaseqc_amd/csrc/rsqc_tin.h"
 
 using namespace rsqc;
 
 namespace {
-template <class F> void launch(uint32_t grid, F &&body) {
-    wavemu::grid_dim().x = grid;
-    for (uint32_t b = 0; b < grid; ++b) { wavemu::block_idx().x = b; wavemu::run_block(RSQC_TIN_THREADS, body); }
-}
 struct State {
     TinPlan plan;
     std::vector<rsqc_tin_row> rows;
@@ -38,33 +31,22 @@ EMU_API void tinemu_set_schedule_seed(unsigned long long seed) { wavemu::set_see
 EMU_API int tinemu_run(int32_t n_contigs, const uint64_t *length, const uint32_t *depth, int32_t n_genes, const uint32_t *seg_off, const int32_t *seg_tid,
                        const uint32_t *seg_start, const uint32_t *seg_end, uint64_t *stats) {
     G = State{};
-    std::vector<uint64_t> off((size_t)n_contigs + 1, 0);
-    std::vector<uint32_t> len32((size_t)n_contigs + 1, 0);
-    for (int32_t t = 0; t < n_contigs; ++t) { len32[(size_t)t] = (uint32_t)length[t]; off[(size_t)t + 1] = off[(size_t)t] + length[t] + 1; }
-    const uint64_t total = off[(size_t)n_contigs];
-    G.error = genebody_check(n_genes, seg_off, seg_tid, seg_start, seg_end, n_contigs, len32.data());
+    gmemu::Input in;
+    G.error = gmemu::lay_out(in, n_contigs, length, depth, n_genes, seg_off, seg_tid, seg_start, seg_end);
     if (!G.error.empty()) return 1;
-    // the scanned array: total + 1 entries, exactly (a read past it is a heap overflow under the sanitizer build)
-    std::vector<uint32_t> S((size_t)total + 1, 0u);
-    size_t at = 0;
-    for (int32_t t = 0; t < n_contigs; ++t)
-        for (uint64_t p = 0; p < length[t]; ++p) S[(size_t)(off[(size_t)t] + p) + 1] = depth[at++];
     tin_plan(n_genes, seg_off, seg_start, seg_end, RSQC_TIN_ITEM, G.plan);
     const uint64_t n_items = G.plan.items.size();
     const uint32_t grid = (uint32_t)((n_items + RSQC_TIN_WAVES - 1) / RSQC_TIN_WAVES);
-    // (the model's columns, the plan, the slots and the rows at exactly their size as well; slots and rows filled with 0xA5: no memset is owed)
-    const size_t n_seg = n_genes ? seg_off[n_genes] : 0;
-    std::vector<int32_t> m_tid(seg_tid, seg_tid + n_seg); std::vector<uint32_t> m_start(seg_start, seg_start + n_seg), m_end(seg_end, seg_end + n_seg);
+    // (the plan, the slots and the rows at exactly their size as well; slots and rows filled with 0xA5: no memset is owed)
     std::vector<TinItem> items(G.plan.items);
     std::vector<uint64_t> item_off(G.plan.item_off);
     std::vector<rsqc_tin_row> part((size_t)n_items);
     G.rows.resize((size_t)n_genes);
     if (n_items) memset(part.data(), 0xA5, part.size() * sizeof(rsqc_tin_row));
     if (n_genes) memset(G.rows.data(), 0xA5, G.rows.size() * sizeof(rsqc_tin_row));
-    const TinModel M{m_tid.data(), m_start.data(), m_end.data()};
-    if (grid) launch(grid, [&]() { tin_items_kernel(S.data(), off.data(), M, items.data(), n_items, part.data()); });
+    if (grid) gmemu::launch(grid, RSQC_TIN_THREADS, [&]() { tin_items_kernel(in.S.data(), in.off.data(), in.model(), items.data(), n_items, part.data()); });
     const uint32_t row_grid = ((uint32_t)n_genes + RSQC_TIN_THREADS - 1) / RSQC_TIN_THREADS;
-    if (row_grid) launch(row_grid, [&]() { tin_rows_kernel(part.data(), item_off.data(), (uint32_t)n_genes, G.rows.data()); });
+    if (row_grid) gmemu::launch(row_grid, RSQC_TIN_THREADS, [&]() { tin_rows_kernel(part.data(), item_off.data(), (uint32_t)n_genes, G.rows.data()); });
     stats[0] = (uint64_t)n_genes; stats[1] = G.plan.n_measured; stats[2] = G.plan.model_bases; stats[3] = n_items; stats[4] = grid;
     return 0;
 }
@@ -84,27 +66,14 @@ EMU_API void tinemu_items(uint32_t *out) { if (!G.plan.items.empty()) memcpy(out
 EMU_API void tinemu_item_off(uint64_t *out) { memcpy(out, G.plan.item_off.data(), G.plan.item_off.size() * 8); }
 
 #if defined(TINEMU_MAIN)
-// tin_emu CASEFILE: four 64-bit words (contigs, genes, segments, schedule seed), the lengths (64-bit each), the depth of every
-// position, seg_off, seg_tid, seg_start, seg_end (32-bit each).  Prints the figures, the integer sums over the rows and the bits of
-// the doubles folded into one word, exits 0, or 1 with the failed check.
+// tin_emu CASEFILE (genemodel_emu.h, without reverse bytes).  Prints the figures, the integer sums over the rows and the bits of the
+// doubles folded into one word, exits 0, or 1 with the failed check.
 int main(int argc, char **argv) {
-    if (argc != 2) { fprintf(stderr, "usage: tin_emu CASEFILE\n"); return 2; }
-    FILE *f = fopen(argv[1], "rb");
-    if (!f) { perror(argv[1]); return 2; }
-    uint64_t head[4];
-    if (fread(head, 8, 4, f) != 4) return 2;
-    const size_t nc = (size_t)head[0], ng = (size_t)head[1], ns = (size_t)head[2];
-    std::vector<uint64_t> length(nc);
-    if (nc && fread(length.data(), 8, nc, f) != nc) return 2;
-    size_t positions = 0;
-    for (uint64_t l : length) positions += (size_t)l;
-    std::vector<uint32_t> depth(positions), seg_off(ng + 1), seg_start(ns), seg_end(ns); std::vector<int32_t> seg_tid(ns);
-    if ((positions && fread(depth.data(), 4, positions, f) != positions) || fread(seg_off.data(), 4, ng + 1, f) != ng + 1 ||
-        (ns && (fread(seg_tid.data(), 4, ns, f) != ns || fread(seg_start.data(), 4, ns, f) != ns || fread(seg_end.data(), 4, ns, f) != ns))) { fprintf(stderr, "short case file\n"); return 2; }
-    fclose(f);
-    wavemu::set_seed(head[3]);
+    gmemu::CaseFile C;
+    if (int rc = gmemu::read_case("tin_emu", argc, argv, false, C)) return rc;
+    wavemu::set_seed(C.seed);
     uint64_t st[5] = {0, 0, 0, 0, 0};
-    const int rc = tinemu_run((int32_t)nc, length.data(), depth.data(), (int32_t)ng, seg_off.data(), seg_tid.data(), seg_start.data(), seg_end.data(), st);
+    const int rc = tinemu_run((int32_t)C.length.size(), C.length.data(), C.depth.data(), (int32_t)C.seg_off.size() - 1, C.seg_off.data(), C.seg_tid.data(), C.seg_start.data(), C.seg_end.data(), st);
     unsigned long long sum = 0, covered = 0, peak = 0, bits = 0;
     for (const rsqc_tin_row &r : G.rows) {
         unsigned long long b; memcpy(&b, &r.dlog2d, 8);

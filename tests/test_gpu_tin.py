@@ -143,6 +143,33 @@ def test_second_end_windows_reset_and_a_new_pass(one, monkeypatch):
     assert err.value.code == abi.ERR_ARG and "rsqc_tin_begin must precede" in str(err.value)
 
 
+def test_both_stages_over_two_passes_with_a_growing_model():
+    """A context of its own, so that every buffer starts empty: --gene-body and --tin in one pass over one contig of 200 with one gene
+    of one 100-base segment, then, behind rsqc_reset, over one contig of 5 000 with genes of 99 bases, 100 bases and 4 097 bases in two
+    segments (two items) -- the model's columns, the plans, the sums, the partials and the rows on the device and both page-locked
+    windows grow between the passes.  Sums and rows against the references in both: the integers exactly, the double within
+    tin_ref's bound."""
+    from rnaseqc_amd.model import Batch
+    from tests import track_ref
+    passes = [([200], [(0, [(50, 150)], 0)], tc._pile(0, 40, 60, 3) + tc._pile(0, 100, 50, 2) + [dict(tid=0, pos=60, cigar=[(abi.CIG_M, 20), (abi.CIG_N, 30), (abi.CIG_M, 20)])]),
+              ([5000], [(0, [(10, 109)], 1), (0, [(200, 300)], 0), (0, [(400, 400 + tc.ITEM), (4600, 4601)], 1)], gc._reads(9, 0, 0, 5000, 300) + tc._pile(0, 4600, 1, 9))]
+    e = engine.Engine(abi.default_params())
+    try:
+        e.set_annotation(Annotation.from_rows(["c0", "c1", "c2"], ANN_ROWS))
+        for lengths, genes, recs in passes:
+            batches = [Batch.from_records(recs)]
+            body_model, model = gref.make_model(genes), tc.model_of([(t, segs) for t, segs, _ in genes])
+            depth = ref.depth_arrays(track_ref.track(batches, lengths), lengths)
+            (want, want_info), (body_want, body_info), L = ref.rows(depth, model), gref.sums(depth, body_model), ref.gene_lengths(model)
+            assert want_info["depth_sum"] > 0 and body_info["depth_sum"] > 0
+            got, info, body = _pass(e, lengths, batches, model, genebody=("first", body_model))
+            ref.assert_rows(got, info, want, want_info, L)
+            gref.assert_equal(body[0], body[1], body_want, body_info)
+        assert L.tolist() == [99, 100, tc.ITEM + 1] and (want_info["n_measured"], body_info["n_measured"]) == (3, 2) and int(want["max_depth"][2]) >= 9
+    finally:
+        e.close()
+
+
 @pytest.mark.parametrize("name", list(tc.BROKEN))
 def test_every_model_rule_violated_once(one, name):
     model, word, gene = tc.broken_model(name)

@@ -1,5 +1,5 @@
-"""CPU: --tin.  The two kernels of rnaseqc_amd/csrc/rsqc_tin.h, unmodified, with the header's launch plan and the model check of
-rsqc_genebody.h, on the 64-lane emulation over the edge catalogue (tests/tin_cases.py) against the restatement of the contract
+"""CPU: --tin.  The two kernels of rnaseqc_amd/csrc/rsqc_tin.h, unmodified, with the header's launch plan and the model check and the
+walk of rsqc_genemodel.h, on the 64-lane emulation over the edge catalogue (tests/tin_cases.py) against the restatement of the contract
 (tests/tin_ref.py), round-robin and under seeded schedules: the integers bit for bit, the double within the contract's bound and
 bit-identical across the schedules; the exported plan; every model rule violated once; the same catalogue through a stand-alone
 sanitizer build of the harness; the host arithmetic (TIN, summary, the text of both files) through librsqc_host.so; the command
@@ -83,6 +83,33 @@ def test_plan_of_70000_genes():
     info, items, item_off = emu.plan(model)
     _check_plan(model, items, item_off, info)
     assert info["items"] == tc.MANY and info["workgroups"] == tc.MANY // 4 and info["model_bases"] == tc.MANY
+
+
+def test_the_two_plans_tile_alike():
+    """--tin and --gene-body cut a gene with one function (gene_tile of rsqc_genemodel.h): on one contig of 10 000, genes of 99 bases
+    (measured by --tin alone), 100 (the least --gene-body measures), 4 096 in one segment (one full item) and 4 097 in two (the least
+    with two items; base 4 096 is the second segment's first) -- the tin items of every gene with L >= 100 are words 0..4 of its
+    gene-body items, item_off is contiguous."""
+    from tests.hostemu import genebody as gb_emu
+    model = dict(seg_off=np.array([0, 1, 2, 3, 5], np.uint32), seg_tid=np.zeros(5, np.int32), seg_start=np.array([0, 100, 300, 4500, 8600], np.uint32),
+                 seg_end=np.array([99, 200, 300 + tc.ITEM, 4500 + tc.ITEM, 8601], np.uint32), reverse=np.array([0, 1, 0, 1], np.uint8))
+    assert int(model["seg_end"].max()) <= 10_000
+    L = ref.gene_lengths(model)
+    assert L.tolist() == [99, 100, tc.ITEM, tc.ITEM + 1]
+    info, items, item_off = emu.plan(model)
+    gb_info, gb_items = gb_emu.plan(model)
+    _check_plan(model, items, item_off, info)
+    assert item_off.tolist() == [0, 1, 2, 3, 5] and int(item_off[-1]) == len(items)
+    for g in range(4):
+        mine, theirs = items[items[:, 0] == g], gb_items[gb_items[:, 0] == g]
+        if L[g] >= 100:
+            assert len(mine) and mine.tolist() == theirs[:, :5].tolist(), g
+            assert (theirs[:, 5] == (int(L[g]) | int(model["reverse"][g]) << 31)).all()
+        else:
+            assert mine.tolist() == [[g, 0, 99, 0, 0]] and len(theirs) == 0
+    assert items[1:].tolist() == gb_items[:, :5].tolist()
+    assert items[3:].tolist() == [[3, 0, tc.ITEM, 3, 0], [3, tc.ITEM, tc.ITEM + 1, 4, tc.ITEM]]
+    assert (info["n_measured"], info["model_bases"]) == (4, int(L.sum())) and (gb_info["n_measured"], gb_info["model_bases"]) == (3, int(L[1:].sum()))
 
 
 def test_sum_above_2_pow_32():
