@@ -916,6 +916,52 @@ RSQC_API int rsqc_tin_begin(rsqc_ctx *ctx, int32_t n_genes, const uint32_t *seg_
 RSQC_API int rsqc_tin_end(rsqc_ctx *ctx, rsqc_tin_info *out);
 RSQC_API int rsqc_tin_rows(rsqc_ctx *ctx, uint32_t first_gene, uint32_t n, const rsqc_tin_row **rows);
 
+/* ---- base quality and composition by read cycle (additive to ABI 7) -----------------------------------------------------------
+ * The device decode (rsqc_decode_*) inflates SEQ and QUAL of every record into device memory; with the mode on, one more kernel per
+ * window counts them by read cycle.  No launch, allocation or output of a pass without the calls changes.  No equality with FastQC,
+ * Picard or RSeQC is claimed; tests/cycle_ref.py is the contract's executable form.  The contract, in integers:
+ *   population   records with flag & (0x100 | 0x200 | 0x800) == 0; nothing else gates a record (not the mapping quality, the tag
+ *                filters, rsqc_params.legacy / unpaired, 0x4 or 0x400): every read counts once, unmapped ones included.
+ *   end          e = 1 when flag & 0x1, flag & 0x80 and not flag & 0x40; otherwise e = 0.
+ *   length       L = l_seq (BAM); the length of SEQ, 0 when SEQ is * (SAM).  L = 0 adds 1 to no_seq_records and nothing else.  A BAM
+ *                record whose fixed part does not fit its block_size (32 + l_read_name + 4 n_cigar + (L + 1) / 2 + L), whose l_seq
+ *                is negative or whose l_read_name is 0 contributes nothing (what the decode makes of such a record is unchanged).
+ *   cycle        query index i of [0, L) is cycle c = i when flag & 0x10 == 0 and c = L - 1 - i otherwise (hard clips are not part of
+ *                SEQ and shift nothing).  A base with c >= RSQC_CYCLE_MAX adds 1 to beyond_bases and to nothing else.
+ *   base         columns A C G T other = 0..4.  BAM nibbles 1, 2, 4, 8 are 0, 1, 2, 3, every other nibble 4; SAM bytes A C G T in
+ *                either case are 0, 1, 2, 3, every other byte 4.  Under flag & 0x10 a base b < 4 becomes 3 - b.  base[e][c][b] += 1.
+ *   quality      missing when BAM qual[0] == 0xFF or SAM QUAL is exactly * (also for L = 1): no_qual_records += 1, the bases still
+ *                count.  Otherwise q = the BAM byte, or the SAM byte - 33 with a floor of 0; q > 63 is stored as 63 and adds 1 to
+ *                clamped_quals.  qual[e][c][q] += 1.
+ *   tables       base[RSQC_CYCLE_ENDS][RSQC_CYCLE_MAX][5] and qual[RSQC_CYCLE_ENDS][RSQC_CYCLE_MAX][RSQC_CYCLE_QBINS], uint64_t.
+ *   info         seen_records: every record the pass's windows submitted (== rsqc_decode_info.records) plus those of rsqc_cycles_add;
+ *                records: the population with L > 0; bases: the sum of base; cycles_ms: HIP events around the stage's kernels.
+ *   checks       behind the read-back: bases + beyond_bases equals the sum of L over the population (the device adds it up in one
+ *                more word); for every (e, c) the sum of qual is at most the sum of base.  A violation is RSQC_ERR_HIP.
+ * The tables do not depend on the order of the records, on how the input is cut into calls and windows, on pipelining, or on the
+ * spelling of the input: the same alignments as BAM, plain SAM and BGZF SAM give identical tables.
+ * rsqc_cycles_begin: behind rsqc_create and before the pass's first submit or rsqc_decode_begin* (RSQC_ERR_ARG behind either).  It
+ * allocates the tables -- 2 * 512 * (5 + 64) * 8 bytes and a few words on the device, the same in page-locked host memory; a refusal
+ * is RSQC_ERR_CAPACITY with the sizes.  Only windows of rsqc_decode_submit / rsqc_decode_submit_text are counted: batches that arrive
+ * through rsqc_submit / rsqc_submit_resident carry no SEQ and contribute nothing.  rsqc_cycles_add adds host-computed counts (input whose
+ * bytes never reach the device as bytes: a host reader): base and qual in the layout above (either may be NULL), of `partial` the
+ * fields seen_records, records, no_seq_records, no_qual_records, bases (which must be the sum of `base`), beyond_bases, clamped_quals;
+ * between rsqc_cycles_begin and rsqc_cycles_end.  rsqc_cycles_end: behind the pass's rsqc_decode_end, or behind the last submit of a
+ * pass the host read (RSQC_ERR_ARG while a stream is open); the tables are the context's, in page-locked memory, valid until the mode
+ * ends; a second call returns the same figures without device work.  rsqc_reset, rsqc_clear_inputs and rsqc_destroy end the mode;
+ * rsqc_reset keeps the allocation.  Not exchanged by rsqc_reduce_* / rsqc_group_*.                                                  */
+#define RSQC_CYCLE_MAX 512
+#define RSQC_CYCLE_QBINS 64
+#define RSQC_CYCLE_ENDS 2
+#define RSQC_CYCLE_BASES 5
+typedef struct rsqc_cycle_info {
+    uint64_t seen_records, records, no_seq_records, no_qual_records, bases, beyond_bases, clamped_quals;
+    double cycles_ms;
+} rsqc_cycle_info;
+RSQC_API int rsqc_cycles_begin(rsqc_ctx *ctx);
+RSQC_API int rsqc_cycles_add(rsqc_ctx *ctx, const uint64_t *base, const uint64_t *qual, const rsqc_cycle_info *partial);
+RSQC_API int rsqc_cycles_end(rsqc_ctx *ctx, rsqc_cycle_info *out, const uint64_t **base, const uint64_t **qual);
+
 RSQC_API const char *rsqc_strerror(int code);
 RSQC_API const char *rsqc_last_error(rsqc_ctx *ctx);
 RSQC_API const char *rsqc_counter_name(int counter);   /* the reference's Metrics key  */

@@ -231,6 +231,15 @@ class TinInfo(C.Structure):
                 ("tin_ms", C.c_double)]
 
 
+# rsqc_cycles_*: the tables are base[CYCLE_ENDS][CYCLE_MAX][CYCLE_BASES] and qual[CYCLE_ENDS][CYCLE_MAX][CYCLE_QBINS], uint64
+CYCLE_MAX, CYCLE_QBINS, CYCLE_ENDS, CYCLE_BASES = 512, 64, 2, 5
+
+
+class CycleInfo(C.Structure):
+    _fields_ = [("seen_records", C.c_uint64), ("records", C.c_uint64), ("no_seq_records", C.c_uint64), ("no_qual_records", C.c_uint64), ("bases", C.c_uint64),
+                ("beyond_bases", C.c_uint64), ("clamped_quals", C.c_uint64), ("cycles_ms", C.c_double)]
+
+
 # rsqc_tin_row, 24 bytes
 TIN_ROW = np.dtype([("depth_sum", np.uint64), ("covered", np.uint32), ("max_depth", np.uint32), ("dlog2d", np.float64)])
 

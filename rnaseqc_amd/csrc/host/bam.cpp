@@ -1,5 +1,6 @@
 #include "bam.hpp"
 #include "../rsqc_bamrec.h"
+#include "../rsqc_cycle.h"
 
 #include <sched.h>
 #include <sys/mman.h>
@@ -55,6 +56,14 @@ rsqc_batch HostBatch::view() {
     return b;
 }
 
+// --cycles: a worker's tables (rsqc_cycle.h's one-thread form) and the records it has seen
+struct BamReader::CycleTab {
+    std::vector<uint64_t> base = std::vector<uint64_t>(rsqc::CYC_BASE_CELLS, 0), qual = std::vector<uint64_t>(rsqc::CYC_QUAL_CELLS, 0);
+    rsqc::CycleCounts counts{base.data(), qual.data(), {0, 0, 0, 0, 0, 0, 0, 0}};
+    uint64_t seen = 0;
+    std::thread::id thread;
+};
+
 BamReader::~BamReader() {
     if (producer_started_) {
         { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
@@ -65,6 +74,7 @@ BamReader::~BamReader() {
     if (map_) munmap(const_cast<uint8_t *>(map_), map_size_);
     if (fp_) fclose(fp_);
     delete pool_;
+    for (CycleTab *t : cycle_tabs_) delete t;
     if (getenv("RSQC_HOST_PROFILE"))
         fprintf(stderr, "[bam] read %.3f  frame-blocks %.3f  inflate %.3f  move %.3f  frame-records %.3f  parse %.3f  merge %.3f s\n",
                 g_t_read, g_t_frame_blocks, g_t_inflate, g_t_move, g_t_frame_rec, g_t_parse, g_t_merge);
@@ -72,6 +82,28 @@ BamReader::~BamReader() {
 
 void BamReader::set_tags(const std::string &chimeric, const std::vector<std::string> &filters) {
     ch_tag_ = chimeric; filter_tags_ = filters;
+}
+
+BamReader::CycleTab *BamReader::cycle_tab_of_this_thread() {        // (once per chunk of 256 KB: the lock is not on a record's path)
+    const std::thread::id me = std::this_thread::get_id();
+    std::lock_guard<std::mutex> lk(cycle_mu_);
+    for (CycleTab *t : cycle_tabs_) if (t->thread == me) return t;
+    CycleTab *t = new CycleTab();
+    t->thread = me;
+    cycle_tabs_.push_back(t);
+    return t;
+}
+void BamReader::cycles_sum(std::vector<uint64_t> &base, std::vector<uint64_t> &qual, rsqc_cycle_info &info) {
+    base.assign(rsqc::CYC_BASE_CELLS, 0); qual.assign(rsqc::CYC_QUAL_CELLS, 0);
+    info = rsqc_cycle_info{};
+    std::lock_guard<std::mutex> lk(cycle_mu_);
+    for (const CycleTab *t : cycle_tabs_) {
+        for (size_t k = 0; k < base.size(); ++k) { base[k] += t->base[k]; info.bases += t->base[k]; }
+        for (size_t k = 0; k < qual.size(); ++k) qual[k] += t->qual[k];
+        const uint64_t *s = t->counts.s;
+        info.seen_records += t->seen; info.records += s[rsqc::CYC_S_RECORDS]; info.no_seq_records += s[rsqc::CYC_S_NO_SEQ];
+        info.no_qual_records += s[rsqc::CYC_S_NO_QUAL]; info.beyond_bases += s[rsqc::CYC_S_BEYOND]; info.clamped_quals += s[rsqc::CYC_S_CLAMPED];
+    }
 }
 
 static inline uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -709,6 +741,12 @@ size_t BamReader::read_batch(HostBatch &out, size_t max_records) {
             memcpy(oqh2 + base + rec0[c], o.qh2.data(), m * sizeof(uint32_t));
             if (oumi) memcpy(oumi + base + rec0[c], o.umi.data(), m * sizeof(uint64_t));
             if (!o.cig.empty()) memcpy(ocig + cig_base + cig0[c], o.cig.data(), o.cig.size() * sizeof(uint32_t));
+            if (cycles_) {                                               // the chunk's records are final here: hop over them once more
+                CycleTab *t = cycle_tab_of_this_thread();
+                size_t q = o.start;
+                for (size_t k = 0; k < m; ++k) { const uint32_t bs = le32(bufp + q); (void)rsqc::cycle_count_bam(bufp + q, bs, t->counts); q += 4 + (size_t)bs; }
+                t->seen += m;
+            }
         });
         g_t_parse += now_s() - tp;
         const double tg = now_s();

@@ -131,6 +131,10 @@ public:
     void set_tags(const std::string &chimeric, const std::vector<std::string> &filters);
     // --umi-tag / --umi-qname: source (RSQC_UMI_SOURCE_*), the tag's two letters, the name's separator; the batches then carry rsqc_batch.umi
     void set_umi(int source, char t0, char t1, char sep) { umi_src_ = (uint8_t)source; umi_t0_ = (uint8_t)t0; umi_t1_ = (uint8_t)t1; umi_sep_ = (uint8_t)sep; }
+    // --cycles: every worker counts SEQ / QUAL of the records it copies into a batch by read cycle (rsqc_cycle.h, the definition the
+    // device kernels run), into tables of its own; cycles_sum adds them up (the layout and the info fields of rsqc_cycles_add)
+    void set_cycles(bool on) { cycles_ = on; }
+    void cycles_sum(std::vector<uint64_t> &base, std::vector<uint64_t> &qual, rsqc_cycle_info &info);
     // appends up to max_records records to `out`; returns the number appended (0 at EOF)
     size_t read_batch(HostBatch &out, size_t max_records);
     uint64_t records_read() const { return n_read_; }
@@ -187,6 +191,11 @@ private:
     std::vector<std::string> filter_tags_;
     uint8_t umi_src_ = 0, umi_t0_ = 0, umi_t1_ = 0, umi_sep_ = 0;
     uint64_t n_read_ = 0;
+    bool cycles_ = false;
+    struct CycleTab;                                    // one worker's tables
+    std::vector<CycleTab *> cycle_tabs_;                // (owned; a worker takes its own once, under cycle_mu_)
+    std::mutex cycle_mu_;
+    CycleTab *cycle_tab_of_this_thread();
     bool have_q_ = false; int32_t q_tid_ = 0, q_pos_ = 0;      // last primary mapped record seen (sort check across batches)
 };
 

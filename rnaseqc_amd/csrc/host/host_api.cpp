@@ -107,6 +107,35 @@ HAPI int host_tin_profile(uint64_t n, const uint32_t *gene_len, const rsqc_tin_r
     return 0;
 }
 
+// --cycles: the two files as the command line writes them (either path may be NULL), from base[2][512][5] and qual[2][512][64].
+// 0, or 8 when a file could not be written
+HAPI int host_cycle_files(const uint64_t *base, const uint64_t *qual, const char *bases_path, const char *quality_path) {
+    if (bases_path && !write_cycle_bases(bases_path, base)) return 8;
+    if (quality_path && !write_cycle_quality(quality_path, base, qual)) return 8;
+    return 0;
+}
+// --cycles: a BAM file through the host reader with set_cycles; the sums as rsqc_cycles_add takes them.  Returns the records read, -1:
+// cannot open, -2: the reader threw
+HAPI long long host_bam_cycles(const char *path, int threads, size_t batch_records, uint64_t *base, uint64_t *qual, rsqc_cycle_info *info) {
+    try {
+        BamReader r;
+        if (threads > 0) r.set_threads(threads);
+        r.set_cycles(true);
+        if (!r.open(path)) return -1;
+        long long n = 0;
+        for (;;) {
+            HostBatch b;
+            const size_t k = r.read_batch(b, batch_records ? batch_records : 65536);
+            if (!k) break;
+            n += (long long)k;
+        }
+        std::vector<uint64_t> vb, vq;
+        r.cycles_sum(vb, vq, *info);
+        memcpy(base, vb.data(), vb.size() * 8); memcpy(qual, vq.data(), vq.size() * 8);
+        return n;
+    } catch (std::exception &) { return -2; }
+}
+
 HAPI unsigned host_library_complexity(double dup, double unique, double limit) { return library_complexity(dup, unique, limit); }
 
 struct BamHandle { BamReader reader; HostBatch batch; rsqc_batch view; std::vector<std::string> names; };

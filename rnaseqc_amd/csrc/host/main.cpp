@@ -56,6 +56,7 @@ struct Options {
     bool bedgraph = false;             // --bedgraph (extension): the per-base coverage track, <sample>.coverage.bedgraph (rsqc_track_begin / _end / _text)
     bool gene_body = false;            // --gene-body (extension): coverage along the gene body in 100 bins, <sample>.gene_body.tsv (rsqc_genebody_begin / _end / _sums; turns the track on)
     bool tin = false;                  // --tin (extension): per-gene transcript integrity from the coverage track, <sample>.tin.tsv and <sample>.tin_summary.tsv (rsqc_tin_begin / _end / _rows; turns the track on)
+    bool cycles = false;               // --cycles (extension): base quality and composition by read cycle, <sample>.cycle_bases.tsv and <sample>.cycle_quality.tsv (rsqc_cycles_begin / _add / _end)
     bool junctions = false;            // --junctions (extension): reads per splice junction, <sample>.junctions.tsv (rsqc_junctions_begin / rsqc_junctions_end)
     bool mark_duplicates = false;      // --mark-duplicates (extension, implies --sort): flag 0x400 rewritten on the GPU before the records are counted (rsqc_markdup_begin / rsqc_markdup_end)
     // --umi-tag=XX / --umi-qname[=C] (extensions, each implies --mark-duplicates): the UMI joins the duplicate signature (rsqc_markdup_use_umi);
@@ -104,7 +105,8 @@ void usage(std::ostream &o) {
          "      --junctions                       (extension) Count reads per splice junction on the GPU and write [sample].junctions.tsv (one GPU)\n"
          "      --bedgraph                        (extension) Build the per-base coverage track on the GPU and write [sample].coverage.bedgraph (one GPU; needs LN in the header)\n"
          "      --gene-body                       (extension) Sum the coverage along every gene's body, 5' to 3' in 100 bins, on the GPU and write [sample].gene_body.tsv (one GPU; needs LN in the header)\n"
-         "      --tin                             (extension) Measure every gene's transcript integrity (TIN: the evenness of its coverage) on the GPU and write [sample].tin.tsv and [sample].tin_summary.tsv (one GPU; needs LN in the header)\n";
+         "      --tin                             (extension) Measure every gene's transcript integrity (TIN: the evenness of its coverage) on the GPU and write [sample].tin.tsv and [sample].tin_summary.tsv (one GPU; needs LN in the header)\n"
+         "      --cycles                          (extension) Count base composition and base quality by read cycle on the GPU, from the SEQ and QUAL the decode already holds, and write [sample].cycle_bases.tsv and [sample].cycle_quality.tsv (one GPU)\n";
 }
 
 long to_long(const std::string &flag, const std::string &v) {
@@ -192,6 +194,7 @@ Options parse(int argc, char **argv) {
         else if (name == "bedgraph") o.bedgraph = true;
         else if (name == "gene-body") o.gene_body = true;
         else if (name == "tin") o.tin = true;
+        else if (name == "cycles") o.cycles = true;
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
         else if (name == "detection-threshold") o.detection = to_ulong(name, need());
         else throw ParseError("Flag could not be matched: " + name);
@@ -840,6 +843,8 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         const GeneBodyModel &m = S.gene_body;
         if ((rc = rsqc_tin_begin(gpu, (int32_t)m.gene_len.size(), m.seg_off.data(), m.seg_tid.data(), m.seg_start.data(), m.seg_end.data())) != RSQC_OK) return gpu_failed(rc);
     }
+    // --cycles: every decode window leaves the counts of its records' SEQ / QUAL by read cycle on the device; the host reader counts its own
+    if (o.cycles && (rc = rsqc_cycles_begin(gpu)) != RSQC_OK) return gpu_failed(rc);
     if (sam_input) {
         // ---- SAM text: the host reads the file (plain) or frames its BGZF blocks, the device does the rest
         rsqc_decode_info di{};
@@ -897,6 +902,7 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
             }
         }
         BamReader &bam = *in.reader;
+        bam.set_cycles(o.cycles);
         int cur = 0; bool in_flight = false;
         for (;;) {
             HostBatch &hb = S.bufs[cur];
@@ -917,7 +923,17 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
             cur ^= 1;
             if (o.verbosity > 1) cout << "Alignments processed: " << alignmentCount << endl;
         }
+        if (o.cycles && rc == RSQC_OK) {                   // the records never reached the device as bytes: the reader's sums are added
+            std::vector<uint64_t> base, qual;
+            rsqc_cycle_info partial{};
+            bam.cycles_sum(base, qual, partial);
+            rc = rsqc_cycles_add(gpu, base.data(), qual.data(), &partial);
+        }
     }
+    // (the stage ran at ingest: under --sort and --mark-duplicates the tables are those of the input)
+    rsqc_cycle_info cycles{};
+    const uint64_t *cycle_base = nullptr, *cycle_qual = nullptr;   // (the context's, until its next reset: the files are written below, before it)
+    if (o.cycles && rc == RSQC_OK) rc = rsqc_cycles_end(gpu, &cycles, &cycle_base, &cycle_qual);
     rsqc_sort_info sort_info{};
     if (o.sort && rc == RSQC_OK && (rc = rsqc_sort_end(gpu, &sort_info)) == RSQC_OK) {
         // the contigs in the order the SORTED records visit them: tid as unsigned, each once (the order of coverage.tsv)
@@ -985,6 +1001,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (o.tin)
             cout << "TIN: genes " << tin.n_genes << ", measured " << tin.n_measured << ", eligible " << tin_values.eligible << ", model_bases " << tin.model_bases
                  << ", covered_bases " << tin.covered_bases << ", depth_sum " << tin.depth_sum << ", median " << tin_values.median << ", tin_ms " << tin.tin_ms << endl;
+        if (o.cycles)
+            cout << "Cycles: records " << cycles.records << ", no_seq " << cycles.no_seq_records << ", no_qual " << cycles.no_qual_records << ", bases " << cycles.bases
+                 << ", beyond " << cycles.beyond_bases << ", clamped " << cycles.clamped_quals << ", cycles_ms " << cycles.cycles_ms << endl;
         cout << "Estimating library complexity..." << endl;
         cout << "Generating report" << endl;
     }
@@ -1009,6 +1028,11 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         const std::string stem = out_dir + "/" + sample.name;
         if (!write_tin(stem + ".tin.tsv", ann.gene_list, S.gene_body.gene_len.data(), tin_rows, tin_values)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".tin.tsv" << endl; return 8; }
         if (!write_tin_summary(stem + ".tin_summary.tsv", tin_values)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".tin_summary.tsv" << endl; return 8; }
+    }
+    if (o.cycles) {
+        const std::string stem = out_dir + "/" + sample.name;
+        if (!write_cycle_bases(stem + ".cycle_bases.tsv", cycle_base)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".cycle_bases.tsv" << endl; return 8; }
+        if (!write_cycle_quality(stem + ".cycle_quality.tsv", cycle_base, cycle_qual)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".cycle_quality.tsv" << endl; return 8; }
     }
     if (!S.async_reports) {
         S.t_rep0 = Clock::now();
@@ -1339,6 +1363,12 @@ int main(int argc, char **argv) {
             bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
             if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
             if (many_gpus) throw ValidationError("--tin runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
+        }
+        if (o.cycles) {
+            // two tables per context: the tables of shards would only need adding up, but that path is not built
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--cycles runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
         }
         if (o.junctions) {
             // one table per context: the per-contig tables of shards would only need concatenating, but that path is not built

@@ -533,4 +533,49 @@ bool write_tin_summary(const std::string &path, const TinProfile &p) {
     return f.good();
 }
 
+// --cycles: the rows of an end are cycles 1..R, R the highest cycle of the end with a base
+static uint32_t cycle_rows(const uint64_t *base, uint32_t e) {
+    uint32_t rows = 0;
+    for (uint32_t c = 0; c < RSQC_CYCLE_MAX; ++c) {
+        uint64_t total = 0;
+        for (uint32_t b = 0; b < RSQC_CYCLE_BASES; ++b) total += base[((size_t)e * RSQC_CYCLE_MAX + c) * RSQC_CYCLE_BASES + b];
+        if (total) rows = c + 1;
+    }
+    return rows;
+}
+bool write_cycle_bases(const std::string &path, const uint64_t *base) {
+    std::ofstream f(path);
+    f << "end\tcycle\tA\tC\tG\tT\tN\ttotal" << NL;
+    for (uint32_t e = 0; e < RSQC_CYCLE_ENDS; ++e)
+        for (uint32_t c = 0, rows = cycle_rows(base, e); c < rows; ++c) {
+            const uint64_t *cell = base + ((size_t)e * RSQC_CYCLE_MAX + c) * RSQC_CYCLE_BASES;
+            uint64_t total = 0;
+            f << e + 1 << '\t' << c + 1;
+            for (uint32_t b = 0; b < RSQC_CYCLE_BASES; ++b) { f << '\t' << cell[b]; total += cell[b]; }
+            f << '\t' << total << NL;
+        }
+    f.close();
+    return f.good();
+}
+bool write_cycle_quality(const std::string &path, const uint64_t *base, const uint64_t *qual) {
+    std::ofstream f(path);
+    f << "end\tcycle\tbases\tmean\tq25\tmedian\tq75" << NL;
+    for (uint32_t e = 0; e < RSQC_CYCLE_ENDS; ++e)
+        for (uint32_t c = 0, rows = cycle_rows(base, e); c < rows; ++c) {
+            const uint64_t *cell = qual + ((size_t)e * RSQC_CYCLE_MAX + c) * RSQC_CYCLE_QBINS;
+            uint64_t n = 0, weighted = 0;
+            for (uint32_t q = 0; q < RSQC_CYCLE_QBINS; ++q) { n += cell[q]; weighted += (uint64_t)q * cell[q]; }
+            uint32_t quant[3] = {0, 0, 0};
+            for (uint32_t k = 1; k <= 3 && n; ++k) {                     // the smallest q with 4 cum(q) >= k n
+                uint64_t cum = 0;
+                for (uint32_t q = 0; q < RSQC_CYCLE_QBINS; ++q) { cum += cell[q]; if (4 * cum >= (uint64_t)k * n) { quant[k - 1] = q; break; } }
+            }
+            char mean[64];
+            snprintf(mean, sizeof mean, "%.6f", n ? (double)weighted / (double)n : 0.0);
+            f << e + 1 << '\t' << c + 1 << '\t' << n << '\t' << mean << '\t' << quant[0] << '\t' << quant[1] << '\t' << quant[2] << NL;
+        }
+    f.close();
+    return f.good();
+}
+
 }  // namespace rsqc_host

@@ -80,4 +80,12 @@ bool write_tin(const std::string &path, const std::vector<std::string> &gene_ids
 // <output>/<sample>.tin_summary.tsv: genes, eligible, mean, median, stdev -- one row
 bool write_tin_summary(const std::string &path, const TinProfile &profile);
 
+// --cycles: the two tables of rsqc_cycles_end, base[2][512][5] and qual[2][512][64].  For end 1 then 2, one row per cycle 1..R, R the
+// highest cycle of that end with a base (a single-end run has no rows of end 2).
+// <output>/<sample>.cycle_bases.tsv: end, cycle, A, C, G, T, N, total
+bool write_cycle_bases(const std::string &path, const uint64_t *base);
+// <output>/<sample>.cycle_quality.tsv: end, cycle, bases (n: the qualities of the cycle), mean (sum of q qual / n in doubles, %.6f), q25, median,
+// q75 (quantile k: the smallest q with 4 cum(q) >= k n); all four 0 for n = 0
+bool write_cycle_quality(const std::string &path, const uint64_t *base, const uint64_t *qual);
+
 }  // namespace rsqc_host

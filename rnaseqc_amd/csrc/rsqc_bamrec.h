@@ -6,7 +6,7 @@
 //   core fields, QNAME                          src/RNASeQC.cpp:245-330, src/Expression.cpp:383-386
 //   NM (GetIntTag), chimeric tag (readStringTag), --tag filters (GetTag)   src/RNASeQC.cpp:258,279,295,319-328,780-800
 //   the CIGAR, put back from the CG tag by htslib when it has more than 65535 operations (bam_tag2cigar)
-// SEQ and QUAL are never read.
+// SEQ and QUAL are never read by the reference's metrics; --cycles (rsqc_cycle.h) reads them, located by bam_seq_layout below.
 #pragma once
 
 #include <stdint.h>
@@ -132,6 +132,22 @@ RSQC_BAM_FN bool bam_record_ops(const uint8_t *rec, uint32_t block_size, uint32_
     return true;
 }
 
+// Where SEQ and QUAL of a record lie: byte offsets from rec (the block_size field) and L = l_seq.  false: l_seq is negative or the
+// fixed part does not fit the record, 32 + l_read_name + 4 n_cigar + (L + 1) / 2 + L <= block_size -- the bound bam_parse_record
+// reaches the aux tail with (it calls this function: the two cannot drift).  Behind a true, [rec + seq_off, rec + qual_off + L) lies
+// inside [rec + 4, rec + 4 + block_size).
+RSQC_BAM_FN bool bam_seq_layout(const uint8_t *rec, uint32_t block_size, uint32_t &seq_off, uint32_t &qual_off, uint32_t &L) {
+    if (block_size < 32) return false;
+    const uint8_t *r = rec + 4;
+    const uint32_t l_name = r[8], n_cigar = bam_ld16(r + 12);
+    const int32_t l_seq = (int32_t)bam_ld32(r + 16);
+    if (l_seq < 0) return false;
+    const uint64_t seq = 32ull + l_name + 4ull * n_cigar, qual = seq + (uint64_t)(l_seq + 1ll) / 2;
+    if (qual + (uint64_t)l_seq > block_size) return false;
+    seq_off = 4u + (uint32_t)seq; qual_off = 4u + (uint32_t)qual; L = (uint32_t)l_seq;
+    return true;
+}
+
 struct BamRecOut {
     rsqc_rec_core core;          // cigar_off is the caller's
     rsqc_rec_aux aux;
@@ -188,7 +204,11 @@ RSQC_BAM_FN bool bam_parse_record(const uint8_t *rec, uint32_t block_size, const
     uint32_t tagbits = (tid == mtid) ? RSQC_TB_MTID_SAME : 0;
     int32_t nm = 0;
     bool umi_open = tags.umi_src == RSQC_UMI_TAG;                                   // the first field of that name counts
-    const uint64_t aux_at = 32ull + l_name + 4ull * n_cigar + (uint64_t)((l_seq < 0 ? 0 : l_seq + 1) / 2) + (uint64_t)(l_seq < 0 ? 0 : l_seq);
+    // the aux tail starts behind QUAL (bam_seq_layout); a negative l_seq stands for no SEQ here, a fixed part that does not fit for no tail
+    uint32_t seq_off, qual_off, seq_len;
+    uint64_t aux_at;
+    if (bam_seq_layout(rec, block_size, seq_off, qual_off, seq_len)) aux_at = (uint64_t)qual_off - 4u + seq_len;
+    else aux_at = l_seq < 0 ? 32ull + l_name + 4ull * n_cigar : ~0ull;
     if (aux_at <= block_size) {
         for (const uint8_t *q = r + aux_at; q + 3 <= end_r;) {
             const char t0 = (char)q[0], t1 = (char)q[1], type = (char)q[2];

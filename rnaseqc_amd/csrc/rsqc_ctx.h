@@ -210,6 +210,19 @@ struct TinState : GeneStage {
     HostBuf h_rows;                                    // every gene's row behind rsqc_tin_end
 };
 
+// --cycles (rsqc_cycles_begin / rsqc_cycles_add / rsqc_cycles_end, rsqc_cycle_api.cpp): the tables and their scalar words on the device
+// (CYC_TABLE_WORDS of 64 bits), the same in page-locked memory behind rsqc_cycles_end, what the host added
+struct CycleState {
+    bool active = false, done = false;
+    DevBuf tab;
+    HostBuf h_tab;
+    uint64_t seen = 0;                                 // records of the pass's decode windows
+    std::vector<uint64_t> added;                       // rsqc_cycles_add: CYC_TABLE_WORDS once there is something, summed on the host
+    uint64_t added_seen = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;   // around every window's kernel
+    rsqc_cycle_info info{};
+};
+
 }  // namespace rsqc
 using namespace rsqc;            // (every unit that sees this header is host code of the library)
 
@@ -306,6 +319,7 @@ struct rsqc_ctx {
     TrackState track;
     GenebodyState genebody;
     TinState tin;
+    CycleState cyc;
     MarkdupState markdup;
 
     // host results
@@ -359,6 +373,9 @@ void track_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forge
 void genebody_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the model and the sums
 // --tin: the stage behind rsqc_track_end (rsqc_tin_api.cpp)
 void tin_drop(rsqc_ctx *c, bool free_buffers);        // ends the mode and forgets the model and the rows
+// --cycles: the window's kernel behind its parse stage, on the main stream (rsqc_cycle_api.cpp; sam: W is pend_s.W)
+int cycle_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
+void cycle_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forgets the counts
 // what the two have in common (rsqc_genemodel_api.cpp).  who: the public call, for the texts; what: the stage, as the texts name it.
 // A begin behind its own argument checks (the order of the calls, the model against the track's contigs; n_seg: its segments), the
 // figures its capacity texts end with, the model and the items reserved and copied (stream order: the caller synchronises); an end

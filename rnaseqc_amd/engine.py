@@ -94,6 +94,9 @@ def load_library():
         lib.rsqc_tin_begin.argtypes = [vp, C.c_int32] + [vp] * 4
         lib.rsqc_tin_end.argtypes = [vp, C.POINTER(abi.TinInfo)]
         lib.rsqc_tin_rows.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+        lib.rsqc_cycles_begin.argtypes = [vp]
+        lib.rsqc_cycles_add.argtypes = [vp, vp, vp, C.POINTER(abi.CycleInfo)]
+        lib.rsqc_cycles_end.argtypes = [vp, C.POINTER(abi.CycleInfo), C.POINTER(vp), C.POINTER(vp)]
         _lib = lib
     return _lib
 
@@ -109,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_track_begin", "rsqc_track_end", "rsqc_track_rows", "rsqc_track_text",
     "rsqc_genebody_begin", "rsqc_genebody_end", "rsqc_genebody_sums",
     "rsqc_tin_begin", "rsqc_tin_end", "rsqc_tin_rows",
+    "rsqc_cycles_begin", "rsqc_cycles_add", "rsqc_cycles_end",
 ]
 
 
@@ -413,6 +417,31 @@ class Engine:
         if not int(n):
             return np.zeros(0, abi.TIN_ROW)
         return abi._view(p.value, int(n) * abi.TIN_ROW.itemsize, np.uint8).copy().view(abi.TIN_ROW)
+
+    # ---- base quality and composition by read cycle (rsqc_cycles_*) -------------------------------------------------------
+    def cycles_begin(self):
+        """Before the pass's first submit or decode_begin: every decode window from here on is counted by read cycle."""
+        self._check(self._l.rsqc_cycles_begin(self._h))
+
+    def cycles_add(self, base, qual, info: dict):
+        """Host-computed counts: base [2][512][5] and qual [2][512][64] (uint64, either may be None) and the fields of rsqc_cycle_info."""
+        b = None if base is None else np.ascontiguousarray(base, dtype=np.uint64).reshape(-1)
+        q = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint64).reshape(-1)
+        assert b is None or b.size == abi.CYCLE_ENDS * abi.CYCLE_MAX * abi.CYCLE_BASES
+        assert q is None or q.size == abi.CYCLE_ENDS * abi.CYCLE_MAX * abi.CYCLE_QBINS
+        part = abi.CycleInfo()
+        for f, _ in abi.CycleInfo._fields_:
+            setattr(part, f, info.get(f, 0))
+        self._check(self._l.rsqc_cycles_add(self._h, abi.ptr(b), abi.ptr(q), C.byref(part)))
+
+    def cycles_end(self):
+        """Behind decode_end(): (the fields of rsqc_cycle_info, base [2, 512, 5], qual [2, 512, 64]); the tables are copies."""
+        info = abi.CycleInfo()
+        pb, pq = C.c_void_p(), C.c_void_p()
+        self._check(self._l.rsqc_cycles_end(self._h, C.byref(info), C.byref(pb), C.byref(pq)))
+        base = abi._view(pb.value, abi.CYCLE_ENDS * abi.CYCLE_MAX * abi.CYCLE_BASES, np.uint64).copy().reshape(abi.CYCLE_ENDS, abi.CYCLE_MAX, abi.CYCLE_BASES)
+        qual = abi._view(pq.value, abi.CYCLE_ENDS * abi.CYCLE_MAX * abi.CYCLE_QBINS, np.uint64).copy().reshape(abi.CYCLE_ENDS, abi.CYCLE_MAX, abi.CYCLE_QBINS)
+        return {f: getattr(info, f) for f, _ in abi.CycleInfo._fields_}, base, qual
 
     def read_device(self, ptr, count, dtype):
         """count items of dtype from a device pointer of this context (tests): hipMemcpy of the HIP runtime the library itself is
