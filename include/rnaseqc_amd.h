@@ -962,6 +962,65 @@ RSQC_API int rsqc_cycles_begin(rsqc_ctx *ctx);
 RSQC_API int rsqc_cycles_add(rsqc_ctx *ctx, const uint64_t *base, const uint64_t *qual, const rsqc_cycle_info *partial);
 RSQC_API int rsqc_cycles_end(rsqc_ctx *ctx, rsqc_cycle_info *out, const uint64_t **base, const uint64_t **qual);
 
+/* ---- errors by read cycle against the reference (additive to ABI 7) ------------------------------------------------------------
+ * With the mode on, one more kernel per decode window walks every record's CIGAR over its SEQ, its QUAL and the reference, which the
+ * device keeps at four bits per base.  No launch, allocation or output of a pass without the calls changes.  No equality with Picard,
+ * RSeQC or samtools stats is claimed; tests/mismatch_ref.py is the contract's executable form.  The contract, in integers (end, cycle,
+ * the base codes of BAM nibbles and SAM bytes, the quality value, its clamp and a missing quality are those of the section above):
+ *   reference    n contigs, the header's @SQ entries in order (the tid space of rsqc_track_begin), each with length[i] and sequence[i]:
+ *                ASCII, or NULL when the FASTA lacks the contig.  Reference code r: A C G T in either case 0..3, every other byte 4.
+ *                On the device: 4 bits per base, 8 bases per 32-bit word (base 8 w + k in bits [4 k, 4 k + 4)), a word offset per contig.
+ *   classes      every record the windows submit is in exactly one, tested in this order:
+ *                1. flag & (0x4 | 0x100 | 0x200 | 0x800) != 0: counted nowhere but in seen_records;
+ *                2. tid outside [0, n) or no sequence for it: no_reference_records;  3. mapq < min_mapq: low_mapq_records;
+ *                4. L = 0: no_seq_records;  5. the lengths of the M I S = X operations do not add up to L (a record without operations
+ *                included): inconsistent_records;  6. otherwise records -- only these touch the tables.
+ *                Nothing else gates a record (not the mapping quality of rsqc_params, the tag filters, legacy, 0x400).  A BAM record whose
+ *                fixed part does not fit its block_size or whose l_read_name is 0 contributes nothing, as in the section above.  A missing
+ *                quality adds 1 to no_qual_records; the bases still count.
+ *   walk         e = the end of flag; query index q = 0; reference position p = pos (64 bits).  The operations in order (a wide record's
+ *                true count; the real CIGAR of a record that keeps it in CG:B,I).  Length 0 does nothing; H, P and codes above 8 do
+ *                nothing.  For a query index i, c = its cycle; a query base with c >= 512 adds 1 to beyond_bases and to nothing else.
+ *                M = X of length n, k in [0, n): b = the raw base code of index q + k (no strand rule), r = the reference code at p + k,
+ *                  4 when p + k < 0 or p + k >= length[tid].  b < 4 and r < 4: compared[e][c] += 1, subst[e][R][B] += 1 with (R, B) =
+ *                  (r, b), or (3 - r, 3 - b) under flag & 0x10 (the matrix reads in the orientation of the sequenced read); b != r:
+ *                  mismatch[e][c] += 1; with qualities, v = the clamped quality (a clamp counts in clamped_quals): byq[v].compared += 1,
+ *                  byq[v].mismatched += 1 on a mismatch.  Otherwise uncompared[e][c] += 1.  Then q += n, p += n.
+ *                I: inserted[e][c] += 1 per base, insertion_events += 1, q += n.      S: clipped[e][c] += 1 per base, q += n.
+ *                D: one event at i = min(q, L - 1): deletions[e][c] += 1 when c < 512; deletion_events += 1, deleted_bases += n, p += n.
+ *                N: p += n.
+ *   tables       uint64_t: cyc[2][512][RSQC_MISMATCH_COLS] with the columns compared, mismatch, uncompared, inserted, clipped,
+ *                deletions; subst[2][4][4] ([end][reference][read]); byq[64][2] ([quality][compared, mismatched]).
+ *   info         seen_records: every record the pass's windows submitted plus those of rsqc_mismatch_add; the class counts; compared ..
+ *                deletions: the sums of the columns; mismatch_ms: HIP events around the stage's kernels.
+ *   checks       behind the read-back (the device sums L over `records` in one more word): compared + uncompared + inserted + clipped +
+ *                beyond_bases equals that sum; mismatch <= compared in every cell; the sum of subst[e] equals the sum of compared[e][.],
+ *                its off-diagonal the sum of mismatch[e][.]; the sum of byq.compared is at most compared.  A violation is RSQC_ERR_HIP
+ *                and voids the pass until rsqc_reset.
+ * The tables do not depend on the order of the records, on how the input is cut into calls and windows, on pipelining, or on the
+ * spelling of the input: the same alignments as BAM, plain SAM and BGZF SAM give identical tables.
+ * rsqc_mismatch_begin: behind rsqc_create and before the pass's first submit or rsqc_decode_begin* (RSQC_ERR_ARG behind either).  It
+ * stages each contig's bases through one buffer (the longest contig, once), packs them on the device (half a byte per base) and allocates
+ * and zeroes the tables (under 60 KB on the device, as much page-locked); a refusal of memory is RSQC_ERR_CAPACITY with the sizes.
+ * sequence == NULL reuses the packed reference of an earlier pass of this context with the same n and length -- it survives rsqc_reset;
+ * RSQC_ERR_ARG when none is kept or n / length differ.  min_mapq: 0..255.  Only windows of rsqc_decode_submit / rsqc_decode_submit_text
+ * are counted: batches through rsqc_submit / rsqc_submit_resident carry no SEQ and contribute nothing.  rsqc_mismatch_add adds
+ * host-computed counts: the tables in the layout above (any may be NULL) and of `partial` every count field; compared .. deletions must
+ * be the sums of the columns of `cyc`.  rsqc_mismatch_end: behind the pass's rsqc_decode_end (RSQC_ERR_ARG while a stream is open); the
+ * tables are the context's, in page-locked memory, valid until the mode ends; a second call returns the same figures without device
+ * work.  rsqc_reset, rsqc_clear_inputs and rsqc_destroy end the mode; rsqc_clear_inputs and rsqc_destroy also free the packed reference.
+ * Not exchanged by rsqc_reduce_* / rsqc_group_*.                                                                                      */
+#define RSQC_MISMATCH_COLS 6
+typedef struct rsqc_mismatch_info {
+    uint64_t seen_records, records, no_reference_records, low_mapq_records, no_seq_records, inconsistent_records, no_qual_records;
+    uint64_t compared, mismatched, uncompared, inserted, clipped, deletions;
+    uint64_t insertion_events, deletion_events, deleted_bases, beyond_bases, clamped_quals;
+    double mismatch_ms;
+} rsqc_mismatch_info;
+RSQC_API int rsqc_mismatch_begin(rsqc_ctx *ctx, int32_t n, const uint64_t *length, const char *const *sequence, uint32_t min_mapq);
+RSQC_API int rsqc_mismatch_add(rsqc_ctx *ctx, const uint64_t *cyc, const uint64_t *subst, const uint64_t *byq, const rsqc_mismatch_info *partial);
+RSQC_API int rsqc_mismatch_end(rsqc_ctx *ctx, rsqc_mismatch_info *out, const uint64_t **cyc, const uint64_t **subst, const uint64_t **byq);
+
 RSQC_API const char *rsqc_strerror(int code);
 RSQC_API const char *rsqc_last_error(rsqc_ctx *ctx);
 RSQC_API const char *rsqc_counter_name(int counter);   /* the reference's Metrics key  */

@@ -240,6 +240,17 @@ class CycleInfo(C.Structure):
                 ("beyond_bases", C.c_uint64), ("clamped_quals", C.c_uint64), ("cycles_ms", C.c_double)]
 
 
+# rsqc_mismatch_*: the tables are cyc[CYCLE_ENDS][CYCLE_MAX][MISMATCH_COLS] (compared, mismatch, uncompared, inserted, clipped, deletions),
+# subst[CYCLE_ENDS][4][4] ([end][reference][read]) and byq[CYCLE_QBINS][2] ([quality][compared, mismatched]), uint64
+MISMATCH_COLS = 6
+
+
+class MismatchInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("seen_records", "records", "no_reference_records", "low_mapq_records", "no_seq_records", "inconsistent_records",
+                                          "no_qual_records", "compared", "mismatched", "uncompared", "inserted", "clipped", "deletions", "insertion_events",
+                                          "deletion_events", "deleted_bases", "beyond_bases", "clamped_quals")] + [("mismatch_ms", C.c_double)]
+
+
 # rsqc_tin_row, 24 bytes
 TIN_ROW = np.dtype([("depth_sum", np.uint64), ("covered", np.uint32), ("max_depth", np.uint32), ("dlog2d", np.float64)])
 

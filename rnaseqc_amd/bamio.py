@@ -206,6 +206,17 @@ def write_bam_fast(path, contigs, batch, ch_tag="ch", filter_tag="XF", threads=1
     return voff
 
 
+def synthetic_reference(tid, length):
+    """The bases of contig `tid` of the synthetic reference that write_bam_fast(seq_mode=2) copies SEQ from (synth_ref_base of the host
+    library's writer, in numpy): uint8 ASCII, `length` of them."""
+    with np.errstate(over="ignore"):
+        x = np.arange(length, dtype=np.uint64) + np.uint64((tid * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF)
+        x ^= x >> np.uint64(31)
+        x *= np.uint64(0xBF58476D1CE4E5B9)
+        x ^= x >> np.uint64(29)
+    return np.frombuffer(b"ACGT", np.uint8)[((x >> np.uint64(61)) & np.uint64(3)).astype(np.intp)]
+
+
 def write_fasta(path, names, reference, line_bases=60, index_path=None):
     """FASTA + .fai for the contigs of a model.Reference (test input for --fasta)."""
     idx = []

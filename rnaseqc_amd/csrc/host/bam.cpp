@@ -1,6 +1,7 @@
 #include "bam.hpp"
 #include "../rsqc_bamrec.h"
 #include "../rsqc_cycle.h"
+#include "../rsqc_mismatch.h"
 
 #include <sched.h>
 #include <sys/mman.h>
@@ -64,6 +65,14 @@ struct BamReader::CycleTab {
     std::thread::id thread;
 };
 
+// --mismatches: the same for rsqc_mismatch.h's one-thread form
+struct BamReader::MismatchTab {
+    std::vector<uint64_t> cyc = std::vector<uint64_t>(rsqc::MM_CYC_CELLS, 0), subst = std::vector<uint64_t>(rsqc::MM_SUBST_CELLS, 0), byq = std::vector<uint64_t>(rsqc::MM_BYQ_CELLS, 0);
+    rsqc::MismatchCounts counts{cyc.data(), subst.data(), byq.data(), {}};
+    uint64_t seen = 0;
+    std::thread::id thread;
+};
+
 BamReader::~BamReader() {
     if (producer_started_) {
         { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
@@ -75,6 +84,7 @@ BamReader::~BamReader() {
     if (fp_) fclose(fp_);
     delete pool_;
     for (CycleTab *t : cycle_tabs_) delete t;
+    for (MismatchTab *t : mismatch_tabs_) delete t;
     if (getenv("RSQC_HOST_PROFILE"))
         fprintf(stderr, "[bam] read %.3f  frame-blocks %.3f  inflate %.3f  move %.3f  frame-records %.3f  parse %.3f  merge %.3f s\n",
                 g_t_read, g_t_frame_blocks, g_t_inflate, g_t_move, g_t_frame_rec, g_t_parse, g_t_merge);
@@ -103,6 +113,35 @@ void BamReader::cycles_sum(std::vector<uint64_t> &base, std::vector<uint64_t> &q
         const uint64_t *s = t->counts.s;
         info.seen_records += t->seen; info.records += s[rsqc::CYC_S_RECORDS]; info.no_seq_records += s[rsqc::CYC_S_NO_SEQ];
         info.no_qual_records += s[rsqc::CYC_S_NO_QUAL]; info.beyond_bases += s[rsqc::CYC_S_BEYOND]; info.clamped_quals += s[rsqc::CYC_S_CLAMPED];
+    }
+}
+
+BamReader::MismatchTab *BamReader::mismatch_tab_of_this_thread() {
+    const std::thread::id me = std::this_thread::get_id();
+    std::lock_guard<std::mutex> lk(cycle_mu_);
+    for (MismatchTab *t : mismatch_tabs_) if (t->thread == me) return t;
+    MismatchTab *t = new MismatchTab();
+    t->thread = me;
+    mismatch_tabs_.push_back(t);
+    return t;
+}
+void BamReader::mismatches_sum(std::vector<uint64_t> &cyc, std::vector<uint64_t> &subst, std::vector<uint64_t> &byq, rsqc_mismatch_info &info) {
+    cyc.assign(rsqc::MM_CYC_CELLS, 0); subst.assign(rsqc::MM_SUBST_CELLS, 0); byq.assign(rsqc::MM_BYQ_CELLS, 0);
+    info = rsqc_mismatch_info{};
+    std::lock_guard<std::mutex> lk(cycle_mu_);
+    for (const MismatchTab *t : mismatch_tabs_) {
+        for (size_t k = 0; k < cyc.size(); ++k) cyc[k] += t->cyc[k];
+        for (size_t k = 0; k < subst.size(); ++k) subst[k] += t->subst[k];
+        for (size_t k = 0; k < byq.size(); ++k) byq[k] += t->byq[k];
+        const uint64_t *s = t->counts.s;
+        info.seen_records += t->seen; info.records += s[rsqc::MM_S_RECORDS]; info.no_reference_records += s[rsqc::MM_S_NO_REF]; info.low_mapq_records += s[rsqc::MM_S_LOW_MAPQ];
+        info.no_seq_records += s[rsqc::MM_S_NO_SEQ]; info.inconsistent_records += s[rsqc::MM_S_INCONSISTENT]; info.no_qual_records += s[rsqc::MM_S_NO_QUAL];
+        info.insertion_events += s[rsqc::MM_S_INS_EVENTS]; info.deletion_events += s[rsqc::MM_S_DEL_EVENTS]; info.deleted_bases += s[rsqc::MM_S_DEL_BASES];
+        info.beyond_bases += s[rsqc::MM_S_BEYOND]; info.clamped_quals += s[rsqc::MM_S_CLAMPED];
+    }
+    for (size_t k = 0; k < cyc.size(); ++k) {
+        uint64_t *col[rsqc::MM_COLS] = {&info.compared, &info.mismatched, &info.uncompared, &info.inserted, &info.clipped, &info.deletions};
+        *col[k % rsqc::MM_COLS] += cyc[k];
     }
 }
 
@@ -745,6 +784,13 @@ size_t BamReader::read_batch(HostBatch &out, size_t max_records) {
                 CycleTab *t = cycle_tab_of_this_thread();
                 size_t q = o.start;
                 for (size_t k = 0; k < m; ++k) { const uint32_t bs = le32(bufp + q); (void)rsqc::cycle_count_bam(bufp + q, bs, t->counts); q += 4 + (size_t)bs; }
+                t->seen += m;
+            }
+            if (mismatches_) {
+                MismatchTab *t = mismatch_tab_of_this_thread();
+                const rsqc::MismatchTextRef ref{mm_seq_.data(), mm_len_.data(), (int32_t)mm_seq_.size()};
+                size_t q = o.start;
+                for (size_t k = 0; k < m; ++k) { const uint32_t bs = le32(bufp + q); (void)rsqc::mismatch_count_bam(bufp + q, bs, ref, mm_min_mapq_, t->counts); q += 4 + (size_t)bs; }
                 t->seen += m;
             }
         });

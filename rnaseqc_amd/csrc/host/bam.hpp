@@ -135,6 +135,13 @@ public:
     // device kernels run), into tables of its own; cycles_sum adds them up (the layout and the info fields of rsqc_cycles_add)
     void set_cycles(bool on) { cycles_ = on; }
     void cycles_sum(std::vector<uint64_t> &base, std::vector<uint64_t> &qual, rsqc_cycle_info &info);
+    // --mismatches: every worker walks the records it copies into a batch over the reference (rsqc_mismatch.h's one-thread form against the
+    // FASTA strings the caller keeps alive: per header contig the bases or NULL, and its length), into tables of its own; mismatches_sum
+    // adds them up (the layouts and the info fields of rsqc_mismatch_add)
+    void set_mismatches(std::vector<const char *> sequence, std::vector<uint64_t> length, uint32_t min_mapq) {
+        mm_seq_ = std::move(sequence); mm_len_ = std::move(length); mm_min_mapq_ = min_mapq; mismatches_ = true;
+    }
+    void mismatches_sum(std::vector<uint64_t> &cyc, std::vector<uint64_t> &subst, std::vector<uint64_t> &byq, rsqc_mismatch_info &info);
     // appends up to max_records records to `out`; returns the number appended (0 at EOF)
     size_t read_batch(HostBatch &out, size_t max_records);
     uint64_t records_read() const { return n_read_; }
@@ -196,6 +203,11 @@ private:
     std::vector<CycleTab *> cycle_tabs_;                // (owned; a worker takes its own once, under cycle_mu_)
     std::mutex cycle_mu_;
     CycleTab *cycle_tab_of_this_thread();
+    bool mismatches_ = false;
+    std::vector<const char *> mm_seq_; std::vector<uint64_t> mm_len_; uint32_t mm_min_mapq_ = 0;
+    struct MismatchTab;                                 // one worker's tables
+    std::vector<MismatchTab *> mismatch_tabs_;          // (owned; a worker takes its own once, under cycle_mu_)
+    MismatchTab *mismatch_tab_of_this_thread();
     bool have_q_ = false; int32_t q_tid_ = 0, q_pos_ = 0;      // last primary mapped record seen (sort check across batches)
 };
 

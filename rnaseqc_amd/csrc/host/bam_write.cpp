@@ -6,6 +6,9 @@
 // seq_mode 0: SEQ all 'A', QUAL 0xff (the contract's BAM).
 // seq_mode 1: random bases and binned Phred-like qualities with runs (the entropy of a real file: inflate costs what it
 //             costs on real data).
+// seq_mode 2: the qualities of seq_mode 1; SEQ copied under the record's CIGAR from the synthetic reference synth_ref_base(tid, position)
+//             -- a function of the position, the FASTA of which bamio.synthetic_reference writes -- with a seeded 0.5 % of the aligned bases
+//             substituted; inserted and clipped bases are random (tools/mismatch_bench.py; the BAM writer only).
 // A batch with the umi column (rsqc_batch.umi) gets an RX:Z aux field behind the others on every record whose key is not 0: the
 // bases the key stands for (the BAM writer only; tools/markdup_umi_bench.py).
 #include <zlib.h>
@@ -68,6 +71,13 @@ void deflate_blocks(const uint8_t *raw, size_t n, std::vector<uint8_t> &comp, st
 }
 
 inline uint64_t xs(uint64_t &s) { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; }
+
+// base 0..3 of the synthetic reference at a position of a contig (bamio.synthetic_reference computes the same in numpy)
+inline uint32_t synth_ref_base(int32_t tid, int64_t pos) {
+    uint64_t x = (uint64_t)pos + (uint64_t)(uint32_t)tid * 0x9E3779B97F4A7C15ull;
+    x ^= x >> 31; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 29;
+    return (uint32_t)(x >> 61) & 3u;
+}
 
 struct Group {
     std::vector<uint8_t> comp;
@@ -164,6 +174,23 @@ HAPI int host_bam_write_ex(const char *path, const char *const *contig_names, co
                     for (size_t k2 = 0; k2 < (l_seq + 1) / 2; k2 += 16) {
                         uint64_t r = xs(s);
                         for (size_t j = k2; j < std::min(k2 + 16, (l_seq + 1) / 2); ++j, r >>= 4) sq[j] = (uint8_t)(base4[r & 3] << 4 | base4[(r >> 2) & 3]);
+                    }
+                    if (seq_mode == 2) {                   // the aligned bases are the reference's, but for 1 in 200 (which becomes one of the other three)
+                        size_t q = 0; int64_t p = co.pos;
+                        const uint32_t *ops = b->cigar + co.cigar_off;
+                        for (uint32_t o = 0; o < nc; ++o) {
+                            const uint32_t code = ops[o] & 15u, n = ops[o] >> 4;
+                            if (code == 0 || code == 7 || code == 8) {
+                                for (uint32_t j = 0; j < n && q < l_seq; ++j, ++q) {
+                                    uint32_t base = synth_ref_base(tid, p + j);
+                                    const uint64_t r = xs(s);
+                                    if (r % 200u == 0) base = (base + 1u + (uint32_t)((r >> 32) % 3u)) & 3u;
+                                    sq[q >> 1] = (q & 1) ? (uint8_t)((sq[q >> 1] & 0xF0u) | base4[base]) : (uint8_t)((sq[q >> 1] & 0x0Fu) | (base4[base] << 4));
+                                }
+                                p += n;
+                            } else if (code == 1 || code == 4) q += n;
+                            else if (code == 2 || code == 3) p += n;
+                        }
                     }
                     // binned qualities with runs: mostly 37, excursions to 25 / 11 / 2 that last a few bases
                     static const uint8_t qbin[8] = {37, 37, 37, 37, 37, 25, 11, 2};

@@ -136,6 +136,37 @@ HAPI long long host_bam_cycles(const char *path, int threads, size_t batch_recor
     } catch (std::exception &) { return -2; }
 }
 
+// --mismatches: the three files as the command line writes them (any path may be NULL), from cyc[2][512][6], subst[2][4][4] and byq[64][2].
+// 0, or 8 when a file could not be written
+HAPI int host_mismatch_files(const uint64_t *cyc, const uint64_t *subst, const uint64_t *byq, const char *cycles_path, const char *types_path, const char *quality_path) {
+    if (cycles_path && !write_mismatch_cycles(cycles_path, cyc)) return 8;
+    if (types_path && !write_mismatch_types(types_path, subst)) return 8;
+    if (quality_path && !write_mismatch_quality(quality_path, byq)) return 8;
+    return 0;
+}
+// --mismatches: a BAM file through the host reader with set_mismatches over n contigs (sequence[i] NULL: the FASTA lacks it); the sums as
+// rsqc_mismatch_add takes them.  Returns the records read, -1: cannot open, -2: the reader threw
+HAPI long long host_bam_mismatches(const char *path, int threads, size_t batch_records, int32_t n, const uint64_t *length, const char *const *sequence, uint32_t min_mapq,
+                                   uint64_t *cyc, uint64_t *subst, uint64_t *byq, rsqc_mismatch_info *info) {
+    try {
+        BamReader r;
+        if (threads > 0) r.set_threads(threads);
+        r.set_mismatches(std::vector<const char *>(sequence, sequence + n), std::vector<uint64_t>(length, length + n), min_mapq);
+        if (!r.open(path)) return -1;
+        long long total = 0;
+        for (;;) {
+            HostBatch b;
+            const size_t k = r.read_batch(b, batch_records ? batch_records : 65536);
+            if (!k) break;
+            total += (long long)k;
+        }
+        std::vector<uint64_t> vc, vs, vq;
+        r.mismatches_sum(vc, vs, vq, *info);
+        memcpy(cyc, vc.data(), vc.size() * 8); memcpy(subst, vs.data(), vs.size() * 8); memcpy(byq, vq.data(), vq.size() * 8);
+        return total;
+    } catch (std::exception &) { return -2; }
+}
+
 HAPI unsigned host_library_complexity(double dup, double unique, double limit) { return library_complexity(dup, unique, limit); }
 
 struct BamHandle { BamReader reader; HostBatch batch; rsqc_batch view; std::vector<std::string> names; };

@@ -57,6 +57,9 @@ struct Options {
     bool gene_body = false;            // --gene-body (extension): coverage along the gene body in 100 bins, <sample>.gene_body.tsv (rsqc_genebody_begin / _end / _sums; turns the track on)
     bool tin = false;                  // --tin (extension): per-gene transcript integrity from the coverage track, <sample>.tin.tsv and <sample>.tin_summary.tsv (rsqc_tin_begin / _end / _rows; turns the track on)
     bool cycles = false;               // --cycles (extension): base quality and composition by read cycle, <sample>.cycle_bases.tsv and <sample>.cycle_quality.tsv (rsqc_cycles_begin / _add / _end)
+    // --mismatches (extension; needs --fasta): errors by read cycle against the reference, <sample>.mismatch_cycles.tsv, .mismatch_types.tsv and
+    // .mismatch_quality.tsv (rsqc_mismatch_begin / _add / _end); --mismatches-mapq=N: the least mapping quality of a counted record, as given
+    bool mismatches = false, has_mismatches_mapq = false; long mismatches_mapq = 0;
     bool junctions = false;            // --junctions (extension): reads per splice junction, <sample>.junctions.tsv (rsqc_junctions_begin / rsqc_junctions_end)
     bool mark_duplicates = false;      // --mark-duplicates (extension, implies --sort): flag 0x400 rewritten on the GPU before the records are counted (rsqc_markdup_begin / rsqc_markdup_end)
     // --umi-tag=XX / --umi-qname[=C] (extensions, each implies --mark-duplicates): the UMI joins the duplicate signature (rsqc_markdup_use_umi);
@@ -106,7 +109,9 @@ void usage(std::ostream &o) {
          "      --bedgraph                        (extension) Build the per-base coverage track on the GPU and write [sample].coverage.bedgraph (one GPU; needs LN in the header)\n"
          "      --gene-body                       (extension) Sum the coverage along every gene's body, 5' to 3' in 100 bins, on the GPU and write [sample].gene_body.tsv (one GPU; needs LN in the header)\n"
          "      --tin                             (extension) Measure every gene's transcript integrity (TIN: the evenness of its coverage) on the GPU and write [sample].tin.tsv and [sample].tin_summary.tsv (one GPU; needs LN in the header)\n"
-         "      --cycles                          (extension) Count base composition and base quality by read cycle on the GPU, from the SEQ and QUAL the decode already holds, and write [sample].cycle_bases.tsv and [sample].cycle_quality.tsv (one GPU)\n";
+         "      --cycles                          (extension) Count base composition and base quality by read cycle on the GPU, from the SEQ and QUAL the decode already holds, and write [sample].cycle_bases.tsv and [sample].cycle_quality.tsv (one GPU)\n"
+         "      --mismatches                      (extension) Walk every record's CIGAR over its SEQ, QUAL and the --fasta reference on the GPU and write [sample].mismatch_cycles.tsv, [sample].mismatch_types.tsv and [sample].mismatch_quality.tsv (one GPU; needs --fasta)\n"
+         "      --mismatches-mapq=[N]             (extension) With --mismatches: the least mapping quality of a counted record, 0..255. Default: 0 (not -q)\n";
 }
 
 long to_long(const std::string &flag, const std::string &v) {
@@ -195,6 +200,8 @@ Options parse(int argc, char **argv) {
         else if (name == "gene-body") o.gene_body = true;
         else if (name == "tin") o.tin = true;
         else if (name == "cycles") o.cycles = true;
+        else if (name == "mismatches") o.mismatches = true;
+        else if (name == "mismatches-mapq") { o.mismatches_mapq = to_long(name, need()); o.has_mismatches_mapq = true; }
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
         else if (name == "detection-threshold") o.detection = to_ulong(name, need());
         else throw ParseError("Flag could not be matched: " + name);
@@ -534,6 +541,9 @@ struct Session {
     JunctionIndex junction_index;                      // --junctions: the annotation's exon boundaries, built once
     GeneBodyModel gene_body; bool gene_body_built = false;      // --gene-body: the model for the header in use (its contigs and their lengths)
     std::vector<uint64_t> gene_body_lengths;
+    // --mismatches: the header (contigs and lengths) the context's packed reference was made for; empty: none is kept
+    bool mismatch_packed = false;
+    std::vector<std::string> mismatch_contigs; std::vector<uint64_t> mismatch_lengths;
     std::future<void> report_job;
     void finish_reports() { if (report_job.valid()) report_job.get(); }
 };
@@ -712,6 +722,21 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
                 for (size_t f = 0; f < flags.size(); ++f) who += std::string(f == 0 ? "" : f + 1 == flags.size() ? " and " : ", ") + flags[f];
                 cerr << S.prefix << who << (flags.size() > 1 ? " need" : " needs") << " the length (LN) of every contig in the header: none for " << bam_contigs[k] << endl; return 10;
             }
+    // --mismatches: per header contig its entry of the FASTA index (-1: the FASTA lacks it); a length that contradicts the header's is refused
+    std::vector<int> mismatch_entry;
+    if (o.mismatches) {
+        mismatch_entry.assign(bam_contigs.size(), -1);
+        for (size_t k = 0; k < bam_contigs.size(); ++k)
+            for (size_t i = 0; i < S.fasta.index.size(); ++i) if (S.fasta.index[i].name == bam_contigs[k]) { mismatch_entry[k] = (int)i; break; }
+        for (size_t k = 0; k < bam_contigs.size(); ++k) {
+            const uint64_t ln = k < in.lengths.size() ? in.lengths[k] : 0;
+            if (mismatch_entry[k] >= 0 && ln && ln != S.fasta.index[(size_t)mismatch_entry[k]].length) {
+                cerr << S.prefix << "--mismatches: contig " << bam_contigs[k] << " has " << ln << " bases in the header (LN) and " << S.fasta.index[(size_t)mismatch_entry[k]].length
+                     << " in the FASTA: this is not the reference the input was aligned to" << endl;
+                return 10;
+            }
+        }
+    }
     const bool same_header = S.flattened && bam_contigs == S.contigs;
     if (!same_header) flatten_for(S, ann, bam_contigs);
     // --gene-body, --tin: the model of this header's contigs and lengths (one for both), built when either changes
@@ -735,6 +760,7 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         // context is as rsqc_create left it (its streams, pools and decode buffers kept)
         if ((rc = rsqc_clear_inputs(gpu)) != RSQC_OK) return gpu_failed(rc);
         S.inputs_set = false; S.dirty = false; S.needs_reset = false;
+        S.mismatch_packed = false;                                         // (the packed reference went with the inputs)
     }
     if (!S.inputs_set) {
         S.dirty = true;                                                    // (a set that fails half-way is cleared before the next one)
@@ -816,6 +842,22 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (di.unsorted) warn_unsorted();
     };
     S.dirty = true;
+    // --mismatches: every decode window leaves the counts of its records' walk over the reference on the device.  The reference is packed for
+    // this header here, in front of the loop's window like the other inputs (a cohort: once, while its contigs and lengths stay)
+    std::vector<const char *> mismatch_seq; std::vector<uint64_t> mismatch_len;
+    if (o.mismatches) {
+        for (size_t k = 0; k < bam_contigs.size(); ++k) {
+            const int i = mismatch_entry[k];
+            mismatch_seq.push_back(i >= 0 ? (const char *)S.fasta_seq[(size_t)i].data() : nullptr);
+            mismatch_len.push_back(i >= 0 ? (uint64_t)S.fasta_seq[(size_t)i].size() : (k < in.lengths.size() ? in.lengths[k] : 0));
+        }
+        const bool kept = S.mismatch_packed && S.mismatch_contigs == bam_contigs && S.mismatch_lengths == mismatch_len;
+        S.mismatch_packed = false;
+        if ((rc = rsqc_mismatch_begin(gpu, n_ref_bam, mismatch_len.data(), kept ? nullptr : mismatch_seq.data(), (uint32_t)o.mismatches_mapq)) != RSQC_OK) return gpu_failed(rc);
+        S.mismatch_packed = true; S.mismatch_contigs = bam_contigs; S.mismatch_lengths = mismatch_len;
+        // one input that the device decodes: the bases live on the device now (a cohort may meet another header, the host reader compares with them)
+        if (!S.async_reports && (sam_input || device_decode)) { std::vector<std::vector<uint8_t>>().swap(S.fasta_seq); mismatch_seq.clear(); }
+    }
     S.t_loop0 = Clock::now();
     rc = RSQC_OK;
     // --sort: the loops below collect (no per-read kernel runs); rsqc_sort_end orders the records and runs them
@@ -903,6 +945,7 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         }
         BamReader &bam = *in.reader;
         bam.set_cycles(o.cycles);
+        if (o.mismatches) bam.set_mismatches(mismatch_seq, mismatch_len, (uint32_t)o.mismatches_mapq);
         int cur = 0; bool in_flight = false;
         for (;;) {
             HostBatch &hb = S.bufs[cur];
@@ -929,11 +972,20 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
             bam.cycles_sum(base, qual, partial);
             rc = rsqc_cycles_add(gpu, base.data(), qual.data(), &partial);
         }
+        if (o.mismatches && rc == RSQC_OK) {
+            std::vector<uint64_t> cyc, subst, byq;
+            rsqc_mismatch_info partial{};
+            bam.mismatches_sum(cyc, subst, byq, partial);
+            rc = rsqc_mismatch_add(gpu, cyc.data(), subst.data(), byq.data(), &partial);
+        }
     }
     // (the stage ran at ingest: under --sort and --mark-duplicates the tables are those of the input)
     rsqc_cycle_info cycles{};
     const uint64_t *cycle_base = nullptr, *cycle_qual = nullptr;   // (the context's, until its next reset: the files are written below, before it)
     if (o.cycles && rc == RSQC_OK) rc = rsqc_cycles_end(gpu, &cycles, &cycle_base, &cycle_qual);
+    rsqc_mismatch_info mismatches{};
+    const uint64_t *mismatch_cyc = nullptr, *mismatch_subst = nullptr, *mismatch_byq = nullptr;
+    if (o.mismatches && rc == RSQC_OK) rc = rsqc_mismatch_end(gpu, &mismatches, &mismatch_cyc, &mismatch_subst, &mismatch_byq);
     rsqc_sort_info sort_info{};
     if (o.sort && rc == RSQC_OK && (rc = rsqc_sort_end(gpu, &sort_info)) == RSQC_OK) {
         // the contigs in the order the SORTED records visit them: tid as unsigned, each once (the order of coverage.tsv)
@@ -1004,6 +1056,11 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (o.cycles)
             cout << "Cycles: records " << cycles.records << ", no_seq " << cycles.no_seq_records << ", no_qual " << cycles.no_qual_records << ", bases " << cycles.bases
                  << ", beyond " << cycles.beyond_bases << ", clamped " << cycles.clamped_quals << ", cycles_ms " << cycles.cycles_ms << endl;
+        if (o.mismatches)
+            cout << "Mismatches: records " << mismatches.records << ", no_reference " << mismatches.no_reference_records << ", low_mapq " << mismatches.low_mapq_records
+                 << ", no_seq " << mismatches.no_seq_records << ", inconsistent " << mismatches.inconsistent_records << ", compared " << mismatches.compared
+                 << ", mismatched " << mismatches.mismatched << ", uncompared " << mismatches.uncompared << ", inserted " << mismatches.inserted << ", clipped " << mismatches.clipped
+                 << ", deletions " << mismatches.deletions << ", beyond " << mismatches.beyond_bases << ", mismatch_ms " << mismatches.mismatch_ms << endl;
         cout << "Estimating library complexity..." << endl;
         cout << "Generating report" << endl;
     }
@@ -1033,6 +1090,12 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         const std::string stem = out_dir + "/" + sample.name;
         if (!write_cycle_bases(stem + ".cycle_bases.tsv", cycle_base)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".cycle_bases.tsv" << endl; return 8; }
         if (!write_cycle_quality(stem + ".cycle_quality.tsv", cycle_base, cycle_qual)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".cycle_quality.tsv" << endl; return 8; }
+    }
+    if (o.mismatches) {
+        const std::string stem = out_dir + "/" + sample.name;
+        if (!write_mismatch_cycles(stem + ".mismatch_cycles.tsv", mismatch_cyc)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".mismatch_cycles.tsv" << endl; return 8; }
+        if (!write_mismatch_types(stem + ".mismatch_types.tsv", mismatch_subst)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".mismatch_types.tsv" << endl; return 8; }
+        if (!write_mismatch_quality(stem + ".mismatch_quality.tsv", mismatch_byq)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".mismatch_quality.tsv" << endl; return 8; }
     }
     if (!S.async_reports) {
         S.t_rep0 = Clock::now();
@@ -1370,6 +1433,15 @@ int main(int argc, char **argv) {
             if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
             if (many_gpus) throw ValidationError("--cycles runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
         }
+        if (o.has_mismatches_mapq && !o.mismatches) throw ValidationError("--mismatches-mapq needs --mismatches");
+        if (o.has_mismatches_mapq && (o.mismatches_mapq < 0 || o.mismatches_mapq > 255)) throw ValidationError("--mismatches-mapq takes a mapping quality of 0..255");
+        if (o.mismatches) {
+            if (!o.has_fasta) throw ValidationError("--mismatches needs the reference: give --fasta");
+            // one set of tables and one packed reference per context: the tables of shards would only need adding up, but that path is not built
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--mismatches runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
+        }
         if (o.junctions) {
             // one table per context: the per-contig tables of shards would only need concatenating, but that path is not built
             bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
@@ -1431,6 +1503,7 @@ int main(int argc, char **argv) {
         if (o.has_fasta) {                                                    // src/RNASeQC.cpp:111-121: GTF openable, then Fasta::open
             { std::ifstream probe(gtf_path); if (!probe.is_open()) { cerr << "Unable to open GTF file: " << gtf_path << endl; return 10; } }
             S.fasta.open(o.fasta);                                            // FileError -> 10
+            if (o.mismatches) S.keep_fasta = true;                            // (--mismatches packs the bases for the input's header, and the host reader compares with them)
             for (auto &e : S.fasta.index) ann.chromosome(e.name);             // the index names join chromosomeMap first (src/Fasta.cpp:93-94)
             if (o.verbosity > 1) cout << "A FASTA has been provided. This will enable GC-content statistics but adds additional runtime and memory costs" << endl;
             Session *sp = &S;

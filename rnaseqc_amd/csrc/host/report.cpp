@@ -578,4 +578,48 @@ bool write_cycle_quality(const std::string &path, const uint64_t *base, const ui
     return f.good();
 }
 
+// --mismatches
+static std::string mismatch_rate(uint64_t mismatches, uint64_t compared) {
+    char text[64];
+    snprintf(text, sizeof text, "%.6f", compared ? (double)mismatches / (double)compared : 0.0);
+    return text;
+}
+bool write_mismatch_cycles(const std::string &path, const uint64_t *cyc) {
+    std::ofstream f(path);
+    f << "end\tcycle\tcompared\tmismatches\tuncompared\tinserted\tclipped\tdeletions\tmismatch_rate" << NL;
+    for (uint32_t e = 0; e < RSQC_CYCLE_ENDS; ++e) {
+        uint32_t rows = 0;                                               // the highest cycle of the end with a non-zero column
+        for (uint32_t c = 0; c < RSQC_CYCLE_MAX; ++c)
+            for (uint32_t k = 0; k < RSQC_MISMATCH_COLS; ++k) if (cyc[((size_t)e * RSQC_CYCLE_MAX + c) * RSQC_MISMATCH_COLS + k]) rows = c + 1;
+        for (uint32_t c = 0; c < rows; ++c) {
+            const uint64_t *cell = cyc + ((size_t)e * RSQC_CYCLE_MAX + c) * RSQC_MISMATCH_COLS;
+            f << e + 1 << '\t' << c + 1;
+            for (uint32_t k = 0; k < RSQC_MISMATCH_COLS; ++k) f << '\t' << cell[k];
+            f << '\t' << mismatch_rate(cell[1], cell[0]) << NL;
+        }
+    }
+    f.close();
+    return f.good();
+}
+bool write_mismatch_types(const std::string &path, const uint64_t *subst) {
+    std::ofstream f(path);
+    f << "end\tref\tread\tcount" << NL;
+    for (uint32_t e = 0; e < RSQC_CYCLE_ENDS; ++e) {
+        uint64_t all = 0;
+        for (uint32_t k = 0; k < 16u; ++k) all += subst[e * 16u + k];
+        if (!all) continue;
+        for (uint32_t k = 0; k < 16u; ++k) f << e + 1 << '\t' << "ACGT"[k / 4u] << '\t' << "ACGT"[k % 4u] << '\t' << subst[e * 16u + k] << NL;
+    }
+    f.close();
+    return f.good();
+}
+bool write_mismatch_quality(const std::string &path, const uint64_t *byq) {
+    std::ofstream f(path);
+    f << "quality\tcompared\tmismatches\tmismatch_rate" << NL;
+    for (uint32_t v = 0; v < RSQC_CYCLE_QBINS; ++v)
+        if (byq[v * 2u]) f << v << '\t' << byq[v * 2u] << '\t' << byq[v * 2u + 1u] << '\t' << mismatch_rate(byq[v * 2u + 1u], byq[v * 2u]) << NL;
+    f.close();
+    return f.good();
+}
+
 }  // namespace rsqc_host

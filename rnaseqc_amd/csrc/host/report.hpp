@@ -88,4 +88,13 @@ bool write_cycle_bases(const std::string &path, const uint64_t *base);
 // q75 (quantile k: the smallest q with 4 cum(q) >= k n); all four 0 for n = 0
 bool write_cycle_quality(const std::string &path, const uint64_t *base, const uint64_t *qual);
 
+// --mismatches: the three tables of rsqc_mismatch_end, cyc[2][512][6], subst[2][4][4] and byq[64][2].
+// <output>/<sample>.mismatch_cycles.tsv: end, cycle, compared, mismatches, uncompared, inserted, clipped, deletions, mismatch_rate (mismatches /
+// compared in doubles, %.6f, 0 for compared = 0); for end 1 then 2, one row per cycle 1..R, R the highest cycle of that end with a non-zero column
+bool write_mismatch_cycles(const std::string &path, const uint64_t *cyc);
+// <output>/<sample>.mismatch_types.tsv: end, ref, read, count; 16 rows (ref then read in A C G T order) per end that has a compared base
+bool write_mismatch_types(const std::string &path, const uint64_t *subst);
+// <output>/<sample>.mismatch_quality.tsv: quality, compared, mismatches, mismatch_rate; one row per quality 0..63 with compared > 0
+bool write_mismatch_quality(const std::string &path, const uint64_t *byq);
+
 }  // namespace rsqc_host

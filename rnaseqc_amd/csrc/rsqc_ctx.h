@@ -223,6 +223,23 @@ struct CycleState {
     rsqc_cycle_info info{};
 };
 
+// --mismatches (rsqc_mismatch_begin / rsqc_mismatch_add / rsqc_mismatch_end, rsqc_mismatch_api.cpp): the reference at four bits per base
+// with a word offset and a length per contig -- kept across rsqc_reset, with the lengths it was packed for on the host --, the tables and
+// their scalar words on the device (MM_TABLE_WORDS of 64 bits), the same in page-locked memory behind rsqc_mismatch_end, what the host added
+struct MismatchState {
+    bool active = false, done = false, have_ref = false;
+    DevBuf ref_words, ref_off, ref_len;
+    std::vector<uint64_t> ref_length;                  // the n lengths of the packed reference
+    uint32_t min_mapq = 0;
+    DevBuf tab;
+    HostBuf h_tab;
+    uint64_t seen = 0;                                 // records of the pass's decode windows
+    std::vector<uint64_t> added;                       // rsqc_mismatch_add: MM_TABLE_WORDS once there is something, summed on the host
+    uint64_t added_seen = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;   // around every window's kernel
+    rsqc_mismatch_info info{};
+};
+
 }  // namespace rsqc
 using namespace rsqc;            // (every unit that sees this header is host code of the library)
 
@@ -320,6 +337,7 @@ struct rsqc_ctx {
     GenebodyState genebody;
     TinState tin;
     CycleState cyc;
+    MismatchState mm;
     MarkdupState markdup;
 
     // host results
@@ -376,6 +394,9 @@ void tin_drop(rsqc_ctx *c, bool free_buffers);        // ends the mode and forge
 // --cycles: the window's kernel behind its parse stage, on the main stream (rsqc_cycle_api.cpp; sam: W is pend_s.W)
 int cycle_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
 void cycle_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forgets the counts
+// --mismatches: the window's kernel behind its parse stage (and behind --cycles'), on the main stream (rsqc_mismatch_api.cpp)
+int mismatch_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
+void mismatch_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the counts; free_buffers: the tables and the packed reference too
 // what the two have in common (rsqc_genemodel_api.cpp).  who: the public call, for the texts; what: the stage, as the texts name it.
 // A begin behind its own argument checks (the order of the calls, the model against the track's contigs; n_seg: its segments), the
 // figures its capacity texts end with, the model and the items reserved and copied (stream order: the caller synchronises); an end

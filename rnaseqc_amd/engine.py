@@ -97,6 +97,9 @@ def load_library():
         lib.rsqc_cycles_begin.argtypes = [vp]
         lib.rsqc_cycles_add.argtypes = [vp, vp, vp, C.POINTER(abi.CycleInfo)]
         lib.rsqc_cycles_end.argtypes = [vp, C.POINTER(abi.CycleInfo), C.POINTER(vp), C.POINTER(vp)]
+        lib.rsqc_mismatch_begin.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_char_p), C.c_uint32]
+        lib.rsqc_mismatch_add.argtypes = [vp, vp, vp, vp, C.POINTER(abi.MismatchInfo)]
+        lib.rsqc_mismatch_end.argtypes = [vp, C.POINTER(abi.MismatchInfo), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         _lib = lib
     return _lib
 
@@ -113,6 +116,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_genebody_begin", "rsqc_genebody_end", "rsqc_genebody_sums",
     "rsqc_tin_begin", "rsqc_tin_end", "rsqc_tin_rows",
     "rsqc_cycles_begin", "rsqc_cycles_add", "rsqc_cycles_end",
+    "rsqc_mismatch_begin", "rsqc_mismatch_add", "rsqc_mismatch_end",
 ]
 
 
@@ -442,6 +446,37 @@ class Engine:
         base = abi._view(pb.value, abi.CYCLE_ENDS * abi.CYCLE_MAX * abi.CYCLE_BASES, np.uint64).copy().reshape(abi.CYCLE_ENDS, abi.CYCLE_MAX, abi.CYCLE_BASES)
         qual = abi._view(pq.value, abi.CYCLE_ENDS * abi.CYCLE_MAX * abi.CYCLE_QBINS, np.uint64).copy().reshape(abi.CYCLE_ENDS, abi.CYCLE_MAX, abi.CYCLE_QBINS)
         return {f: getattr(info, f) for f, _ in abi.CycleInfo._fields_}, base, qual
+
+    # ---- errors by read cycle against the reference (rsqc_mismatch_*) -----------------------------------------------------
+    _MM_SHAPES = ((abi.CYCLE_ENDS, abi.CYCLE_MAX, abi.MISMATCH_COLS), (abi.CYCLE_ENDS, 4, 4), (abi.CYCLE_QBINS, 2))
+
+    def mismatch_begin(self, lengths, sequences, min_mapq=0):
+        """Before the pass's first submit or decode_begin.  lengths: one per @SQ contig; sequences: per contig bytes or None (the FASTA
+        lacks it), or None altogether: the packed reference of an earlier pass of this context is used again."""
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        seqs = None
+        if sequences is not None:
+            assert len(sequences) == ln.size
+            seqs = (C.c_char_p * max(ln.size, 1))(*[None if s is None else bytes(s) for s in sequences])
+        self._check(self._l.rsqc_mismatch_begin(self._h, int(ln.size), abi.ptr(ln), seqs, int(min_mapq)))
+
+    def mismatch_add(self, cyc, subst, byq, info: dict):
+        """Host-computed counts: cyc [2][512][6], subst [2][4][4], byq [64][2] (uint64, any may be None) and the fields of rsqc_mismatch_info."""
+        t = [None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in (cyc, subst, byq)]
+        for a, shape in zip(t, self._MM_SHAPES):
+            assert a is None or a.size == int(np.prod(shape))
+        part = abi.MismatchInfo()
+        for f, _ in abi.MismatchInfo._fields_:
+            setattr(part, f, info.get(f, 0))
+        self._check(self._l.rsqc_mismatch_add(self._h, abi.ptr(t[0]), abi.ptr(t[1]), abi.ptr(t[2]), C.byref(part)))
+
+    def mismatch_end(self):
+        """Behind decode_end(): (the fields of rsqc_mismatch_info, cyc [2, 512, 6], subst [2, 4, 4], byq [64, 2]); the tables are copies."""
+        info = abi.MismatchInfo()
+        p = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        self._check(self._l.rsqc_mismatch_end(self._h, C.byref(info), C.byref(p[0]), C.byref(p[1]), C.byref(p[2])))
+        tabs = [abi._view(q.value, int(np.prod(shape)), np.uint64).copy().reshape(shape) for q, shape in zip(p, self._MM_SHAPES)]
+        return ({f: getattr(info, f) for f, _ in abi.MismatchInfo._fields_}, *tabs)
 
     def read_device(self, ptr, count, dtype):
         """count items of dtype from a device pointer of this context (tests): hipMemcpy of the HIP runtime the library itself is
