@@ -1021,6 +1021,63 @@ RSQC_API int rsqc_mismatch_begin(rsqc_ctx *ctx, int32_t n, const uint64_t *lengt
 RSQC_API int rsqc_mismatch_add(rsqc_ctx *ctx, const uint64_t *cyc, const uint64_t *subst, const uint64_t *byq, const rsqc_mismatch_info *partial);
 RSQC_API int rsqc_mismatch_end(rsqc_ctx *ctx, rsqc_mismatch_info *out, const uint64_t **cyc, const uint64_t **subst, const uint64_t **byq);
 
+/* ---- base counts at known variant sites (additive to ABI 7) ----------------------------------------------------------------------
+ * With the mode on, one more kernel per decode window takes a lane per record and counts which base the record shows at every site of a
+ * sorted list that lies under one of its aligned blocks.  No launch, allocation or output of a pass without the calls changes.  No
+ * equality with GATK ASEReadCounter, samtools mpileup or bcftools is claimed; tests/allele_ref.py is the contract's executable form.
+ * The contract, in integers (the base codes of BAM nibbles and SAM bytes, the quality value and a missing quality are those of the
+ * --cycles section above):
+ *   sites        n_sites pairs (tid[k], pos[k]), 0-based, strictly ascending by (tid, pos) -- so without duplicates --, 0 <= tid <
+ *                n_contigs (the header's @SQ entries in order), 0 <= pos < 2^31 - 1.  n_sites may be 0.  No contig length and no FASTA
+ *                are needed.  On the device: pos[n_sites] and first[n_contigs + 1] (the sites of tid are [first[tid], first[tid + 1])).
+ *   classes      every record the windows submit is in exactly one, tested in this order:
+ *                1. flag & (0x4 | 0x100 | 0x200 | 0x800) != 0: counted nowhere but in seen_records;
+ *                2. tid outside [0, n_contigs): off_contig_records;  3. mapq < min_mapq: low_mapq_records;  4. L = 0: no_seq_records;
+ *                5. the lengths of the M I S = X operations do not add up to L (a record without operations included):
+ *                inconsistent_records;  6. otherwise records -- only these are walked.
+ *                Nothing else gates a record (not the mapping quality of rsqc_params, the tag filters, legacy, 0x400: flagged duplicates
+ *                count; under duplicate marking the stage sees the input's flags).  A BAM record whose fixed part does not fit its
+ *                block_size or whose l_read_name is 0 contributes nothing.  A record of class `records` without qualities adds 1 to
+ *                no_qual_records.
+ *   walk         query index q = 0; reference position p = pos (64 bits).  The operations in order (a wide record's true count; the
+ *                real CIGAR of a record that keeps it in CG:B,I).  Length 0, H, P and codes above 8 do nothing.
+ *                M = X of length n: for every site s of tid with p <= s.pos < p + n: i = q + (s.pos - p), b = the raw base code of
+ *                  index i (no strand complement: SEQ and the alleles of a site are both in reference orientation); with qualities
+ *                  and the quality value of i (the BAM byte, or the SAM byte - 33 floored at 0; no clamp) below min_baseq:
+ *                  low_baseq[s] += 1; otherwise column b of s += 1 for b < 4, other[s] += 1 for b = 4.  A record without qualities
+ *                  passes the quality test.  Then q += n, p += n.
+ *                I, S: q += n; they cover no site.      D: deleted[s] += 1 for every site in [p, p + n); p += n.
+ *                N: p += n; the sites under it get nothing.
+ *   table        uint64_t counts[n_sites][RSQC_ALLELE_COLS] with the columns A C G T other deleted low_baseq.  One observation is one
+ *                increment: the two mates of a pair are two records, and where they overlap a site it is observed twice.
+ *   info         seen_records: every record the pass's windows submitted plus those of rsqc_alleles_add; the class counts;
+ *                hit_records: records of class `records` with at least one observation; observations: the sum of the table;
+ *                alleles_ms: HIP events around the stage's kernels, summed over the windows.
+ *   checks       behind the read-back (the device adds its observations up in one more word, per lane in registers and one sum per
+ *                workgroup): the sum of all cells equals that word plus what rsqc_alleles_add brought; hit_records <= records.  A
+ *                violation is RSQC_ERR_HIP and voids the pass until rsqc_reset.
+ * The table does not depend on the order of the records, on how the input is cut into calls and windows, on pipelining, or on the
+ * spelling of the input: the same alignments as BAM, plain SAM and BGZF SAM give identical tables.
+ * rsqc_alleles_begin: behind rsqc_create and before the pass's first submit or rsqc_decode_begin* (RSQC_ERR_ARG behind either).  A list
+ * that is not strictly ascending, a tid or pos out of range (each message names the first offending index), min_mapq > 255 or
+ * min_baseq > 93 is RSQC_ERR_ARG.  The sites go to the device at every call (4 bytes per site, 4 per contig); the cells are 64 bytes per
+ * site on the device and as much page-locked; a refusal of memory is RSQC_ERR_CAPACITY with the sizes.  Only windows of
+ * rsqc_decode_submit / rsqc_decode_submit_text are counted.  rsqc_alleles_add adds host-computed counts: `counts` in the layout above
+ * (NULL: none) and every count field of `partial`; the sum of `counts` must equal partial->observations (RSQC_ERR_ARG otherwise, and
+ * behind rsqc_alleles_end).  rsqc_alleles_end: behind the pass's rsqc_decode_end (RSQC_ERR_ARG while a stream is open); the table is the
+ * context's, in page-locked memory, valid until the mode ends; a second call returns the same figures without device work.  rsqc_reset
+ * ends the mode and forgets the counts; rsqc_clear_inputs and rsqc_destroy also free the buffers.  Not exchanged by rsqc_reduce_* /
+ * rsqc_group_*.                                                                                                                        */
+#define RSQC_ALLELE_COLS 7
+typedef struct rsqc_allele_info {
+    uint64_t seen_records, records, off_contig_records, low_mapq_records, no_seq_records, inconsistent_records, no_qual_records;
+    uint64_t hit_records, observations, n_sites;
+    double alleles_ms;
+} rsqc_allele_info;
+RSQC_API int rsqc_alleles_begin(rsqc_ctx *ctx, int32_t n_contigs, uint32_t n_sites, const int32_t *tid, const int32_t *pos, uint32_t min_mapq, uint32_t min_baseq);
+RSQC_API int rsqc_alleles_add(rsqc_ctx *ctx, const uint64_t *counts /* [n_sites][RSQC_ALLELE_COLS] or NULL */, const rsqc_allele_info *partial);
+RSQC_API int rsqc_alleles_end(rsqc_ctx *ctx, rsqc_allele_info *out, const uint64_t **counts);
+
 RSQC_API const char *rsqc_strerror(int code);
 RSQC_API const char *rsqc_last_error(rsqc_ctx *ctx);
 RSQC_API const char *rsqc_counter_name(int counter);   /* the reference's Metrics key  */

@@ -251,6 +251,15 @@ class MismatchInfo(C.Structure):
                                           "deletion_events", "deleted_bases", "beyond_bases", "clamped_quals")] + [("mismatch_ms", C.c_double)]
 
 
+# rsqc_alleles_*: the table is counts[n_sites][ALLELE_COLS] (A, C, G, T, other, deleted, low_baseq), uint64
+ALLELE_COLS = 7
+
+
+class AlleleInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("seen_records", "records", "off_contig_records", "low_mapq_records", "no_seq_records", "inconsistent_records",
+                                          "no_qual_records", "hit_records", "observations", "n_sites")] + [("alleles_ms", C.c_double)]
+
+
 # rsqc_tin_row, 24 bytes
 TIN_ROW = np.dtype([("depth_sum", np.uint64), ("covered", np.uint32), ("max_depth", np.uint32), ("dlog2d", np.float64)])
 

@@ -2,6 +2,7 @@
 #include "../rsqc_bamrec.h"
 #include "../rsqc_cycle.h"
 #include "../rsqc_mismatch.h"
+#include "../rsqc_allele.h"
 
 #include <sched.h>
 #include <sys/mman.h>
@@ -73,6 +74,17 @@ struct BamReader::MismatchTab {
     std::thread::id thread;
 };
 
+// --alleles: the cells of the table all workers share, and a worker's scalar words
+struct AlleleSharedCells {
+    uint64_t *counts;
+    void add(uint32_t site, uint32_t col) const { __atomic_fetch_add(&counts[(size_t)site * rsqc::AL_COLS + col], (uint64_t)1, __ATOMIC_RELAXED); }
+};
+struct BamReader::AlleleTab {
+    rsqc::AlleleCounts<AlleleSharedCells> counts{AlleleSharedCells{nullptr}, {}};
+    uint64_t seen = 0;
+    std::thread::id thread;
+};
+
 BamReader::~BamReader() {
     if (producer_started_) {
         { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
@@ -85,6 +97,7 @@ BamReader::~BamReader() {
     delete pool_;
     for (CycleTab *t : cycle_tabs_) delete t;
     for (MismatchTab *t : mismatch_tabs_) delete t;
+    for (AlleleTab *t : allele_tabs_) delete t;
     if (getenv("RSQC_HOST_PROFILE"))
         fprintf(stderr, "[bam] read %.3f  frame-blocks %.3f  inflate %.3f  move %.3f  frame-records %.3f  parse %.3f  merge %.3f s\n",
                 g_t_read, g_t_frame_blocks, g_t_inflate, g_t_move, g_t_frame_rec, g_t_parse, g_t_merge);
@@ -143,6 +156,28 @@ void BamReader::mismatches_sum(std::vector<uint64_t> &cyc, std::vector<uint64_t>
         uint64_t *col[rsqc::MM_COLS] = {&info.compared, &info.mismatched, &info.uncompared, &info.inserted, &info.clipped, &info.deletions};
         *col[k % rsqc::MM_COLS] += cyc[k];
     }
+}
+
+BamReader::AlleleTab *BamReader::allele_tab_of_this_thread() {
+    const std::thread::id me = std::this_thread::get_id();
+    std::lock_guard<std::mutex> lk(cycle_mu_);
+    for (AlleleTab *t : allele_tabs_) if (t->thread == me) return t;
+    AlleleTab *t = new AlleleTab();
+    t->thread = me; t->counts.cells.counts = al_counts_.data();
+    allele_tabs_.push_back(t);
+    return t;
+}
+void BamReader::alleles_sum(std::vector<uint64_t> &counts, rsqc_allele_info &info) {
+    info = rsqc_allele_info{};
+    std::lock_guard<std::mutex> lk(cycle_mu_);
+    counts = al_counts_;
+    for (const AlleleTab *t : allele_tabs_) {
+        const uint64_t *s = t->counts.s;
+        info.seen_records += t->seen; info.records += s[rsqc::AL_S_RECORDS]; info.off_contig_records += s[rsqc::AL_S_OFF_CONTIG]; info.low_mapq_records += s[rsqc::AL_S_LOW_MAPQ];
+        info.no_seq_records += s[rsqc::AL_S_NO_SEQ]; info.inconsistent_records += s[rsqc::AL_S_INCONSISTENT]; info.no_qual_records += s[rsqc::AL_S_NO_QUAL];
+        info.hit_records += s[rsqc::AL_S_HIT]; info.observations += s[rsqc::AL_S_OBS];
+    }
+    info.n_sites = al_pos_.size();
 }
 
 static inline uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -791,6 +826,13 @@ size_t BamReader::read_batch(HostBatch &out, size_t max_records) {
                 const rsqc::MismatchTextRef ref{mm_seq_.data(), mm_len_.data(), (int32_t)mm_seq_.size()};
                 size_t q = o.start;
                 for (size_t k = 0; k < m; ++k) { const uint32_t bs = le32(bufp + q); (void)rsqc::mismatch_count_bam(bufp + q, bs, ref, mm_min_mapq_, t->counts); q += 4 + (size_t)bs; }
+                t->seen += m;
+            }
+            if (alleles_) {
+                AlleleTab *t = allele_tab_of_this_thread();
+                const rsqc::AlleleSites sites{al_pos_.data(), al_first_.data(), (int32_t)al_first_.size() - 1};
+                size_t q = o.start;
+                for (size_t k = 0; k < m; ++k) { const uint32_t bs = le32(bufp + q); (void)rsqc::allele_count_bam(bufp + q, bs, sites, al_min_mapq_, al_min_baseq_, t->counts); q += 4 + (size_t)bs; }
                 t->seen += m;
             }
         });

@@ -142,6 +142,14 @@ public:
         mm_seq_ = std::move(sequence); mm_len_ = std::move(length); mm_min_mapq_ = min_mapq; mismatches_ = true;
     }
     void mismatches_sum(std::vector<uint64_t> &cyc, std::vector<uint64_t> &subst, std::vector<uint64_t> &byq, rsqc_mismatch_info &info);
+    // --alleles: every worker walks the records it copies into a batch over the sites (rsqc_allele.h's one-thread form; pos[n_sites] and
+    // first[n_contigs + 1] as the device holds them) into ONE shared table [site][7] with relaxed atomic adds -- a table per worker would be
+    // 56 bytes per site each --, the scalar words per worker; alleles_sum hands out the table and the info fields of rsqc_alleles_add
+    void set_alleles(std::vector<int32_t> pos, std::vector<uint32_t> first, uint32_t min_mapq, uint32_t min_baseq) {
+        al_pos_ = std::move(pos); al_first_ = std::move(first); al_min_mapq_ = min_mapq; al_min_baseq_ = min_baseq;
+        al_counts_.assign(al_pos_.size() * RSQC_ALLELE_COLS, 0); alleles_ = true;
+    }
+    void alleles_sum(std::vector<uint64_t> &counts, rsqc_allele_info &info);
     // appends up to max_records records to `out`; returns the number appended (0 at EOF)
     size_t read_batch(HostBatch &out, size_t max_records);
     uint64_t records_read() const { return n_read_; }
@@ -208,6 +216,12 @@ private:
     struct MismatchTab;                                 // one worker's tables
     std::vector<MismatchTab *> mismatch_tabs_;          // (owned; a worker takes its own once, under cycle_mu_)
     MismatchTab *mismatch_tab_of_this_thread();
+    bool alleles_ = false;
+    std::vector<int32_t> al_pos_; std::vector<uint32_t> al_first_; uint32_t al_min_mapq_ = 0, al_min_baseq_ = 0;
+    std::vector<uint64_t> al_counts_;                   // the shared table
+    struct AlleleTab;                                   // one worker's scalar words
+    std::vector<AlleleTab *> allele_tabs_;              // (owned; a worker takes its own once, under cycle_mu_)
+    AlleleTab *allele_tab_of_this_thread();
     bool have_q_ = false; int32_t q_tid_ = 0, q_pos_ = 0;      // last primary mapped record seen (sort check across batches)
 };
 

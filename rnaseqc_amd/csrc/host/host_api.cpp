@@ -167,6 +167,61 @@ HAPI long long host_bam_mismatches(const char *path, int threads, size_t batch_r
     } catch (std::exception &) { return -2; }
 }
 
+// --alleles: the site file against n contig names.  tid / pos take up to `cap` sites, lines3 skipped_lines, off_header_lines and
+// duplicate_lines, text one "id<TAB>ref<TAB>alt<LF>" per site (or the message of a malformed line).  Returns the sites, -10: the file
+// cannot be opened, -11: a malformed line, -1: more sites than cap or more text than text_cap
+HAPI long long host_sites_parse(const char *path, int32_t n, const char *const *names, int32_t *tid, int32_t *pos, uint64_t cap, uint64_t *lines3, char *text, uint64_t text_cap) {
+    SiteFile file;
+    std::string error;
+    if (text_cap) text[0] = 0;
+    if (const int rc = read_sites(path, file, error)) {
+        if (text_cap) { strncpy(text, error.c_str(), (size_t)text_cap - 1); text[text_cap - 1] = 0; }
+        return -rc;
+    }
+    ResolvedSites r;
+    resolve_sites(file, std::vector<std::string>(names, names + n), r);
+    lines3[0] = file.skipped_lines; lines3[1] = r.off_header_lines; lines3[2] = r.duplicate_lines;
+    std::string meta;
+    for (uint32_t k : r.line) meta += file.lines[k].id + "\t" + file.lines[k].ref + "\t" + file.lines[k].alt + "\n";
+    if (r.tid.size() > cap || meta.size() + 1 > text_cap) return -1;
+    for (size_t k = 0; k < r.tid.size(); ++k) { tid[k] = r.tid[k]; pos[k] = r.pos[k]; }
+    memcpy(text, meta.c_str(), meta.size() + 1);
+    return (long long)r.tid.size();
+}
+// --alleles: <sample>.allele_counts.tsv as the command line writes it, for the site file against n contig names and counts[n_sites][7] (n_sites
+// as host_sites_parse returns it).  0; 8 when the file could not be written; 10 / 11 as the reader says
+HAPI int host_allele_file(const char *sites_path, int32_t n, const char *const *names, const uint64_t *counts, const char *out_path) {
+    SiteFile file;
+    std::string error;
+    if (const int rc = read_sites(sites_path, file, error)) return rc;
+    const std::vector<std::string> contigs(names, names + n);
+    ResolvedSites r;
+    resolve_sites(file, contigs, r);
+    return write_allele_counts(out_path, contigs, file, r, counts) ? 0 : 8;
+}
+// --alleles: a BAM file through the host reader with set_alleles (pos[n_sites], first[n_contigs + 1]); the shared table and the sums as
+// rsqc_alleles_add takes them.  Returns the records read, -1: cannot open, -2: the reader threw
+HAPI long long host_bam_alleles(const char *path, int threads, size_t batch_records, int32_t n_contigs, uint32_t n_sites, const int32_t *pos, const uint32_t *first,
+                                uint32_t min_mapq, uint32_t min_baseq, uint64_t *counts, rsqc_allele_info *info) {
+    try {
+        BamReader r;
+        if (threads > 0) r.set_threads(threads);
+        r.set_alleles(std::vector<int32_t>(pos, pos + n_sites), std::vector<uint32_t>(first, first + n_contigs + 1), min_mapq, min_baseq);
+        if (!r.open(path)) return -1;
+        long long total = 0;
+        for (;;) {
+            HostBatch b;
+            const size_t k = r.read_batch(b, batch_records ? batch_records : 65536);
+            if (!k) break;
+            total += (long long)k;
+        }
+        std::vector<uint64_t> v;
+        r.alleles_sum(v, *info);
+        if (!v.empty()) memcpy(counts, v.data(), v.size() * 8);
+        return total;
+    } catch (std::exception &) { return -2; }
+}
+
 HAPI unsigned host_library_complexity(double dup, double unique, double limit) { return library_complexity(dup, unique, limit); }
 
 struct BamHandle { BamReader reader; HostBatch batch; rsqc_batch view; std::vector<std::string> names; };

@@ -60,6 +60,9 @@ struct Options {
     // --mismatches (extension; needs --fasta): errors by read cycle against the reference, <sample>.mismatch_cycles.tsv, .mismatch_types.tsv and
     // .mismatch_quality.tsv (rsqc_mismatch_begin / _add / _end); --mismatches-mapq=N: the least mapping quality of a counted record, as given
     bool mismatches = false, has_mismatches_mapq = false; long mismatches_mapq = 0;
+    // --alleles=FILE (extension): base counts at the single-base sites of a VCF, <sample>.allele_counts.tsv (rsqc_alleles_begin / _add / _end);
+    // --allele-mapq=N / --allele-baseq=N: the least mapping quality of a counted record and the least quality of a counted base, as given
+    bool has_alleles = false, has_allele_mapq = false, has_allele_baseq = false; std::string alleles; long allele_mapq = 0, allele_baseq = 0;
     bool junctions = false;            // --junctions (extension): reads per splice junction, <sample>.junctions.tsv (rsqc_junctions_begin / rsqc_junctions_end)
     bool mark_duplicates = false;      // --mark-duplicates (extension, implies --sort): flag 0x400 rewritten on the GPU before the records are counted (rsqc_markdup_begin / rsqc_markdup_end)
     // --umi-tag=XX / --umi-qname[=C] (extensions, each implies --mark-duplicates): the UMI joins the duplicate signature (rsqc_markdup_use_umi);
@@ -111,7 +114,10 @@ void usage(std::ostream &o) {
          "      --tin                             (extension) Measure every gene's transcript integrity (TIN: the evenness of its coverage) on the GPU and write [sample].tin.tsv and [sample].tin_summary.tsv (one GPU; needs LN in the header)\n"
          "      --cycles                          (extension) Count base composition and base quality by read cycle on the GPU, from the SEQ and QUAL the decode already holds, and write [sample].cycle_bases.tsv and [sample].cycle_quality.tsv (one GPU)\n"
          "      --mismatches                      (extension) Walk every record's CIGAR over its SEQ, QUAL and the --fasta reference on the GPU and write [sample].mismatch_cycles.tsv, [sample].mismatch_types.tsv and [sample].mismatch_quality.tsv (one GPU; needs --fasta)\n"
-         "      --mismatches-mapq=[N]             (extension) With --mismatches: the least mapping quality of a counted record, 0..255. Default: 0 (not -q)\n";
+         "      --mismatches-mapq=[N]             (extension) With --mismatches: the least mapping quality of a counted record, 0..255. Default: 0 (not -q)\n"
+         "      --alleles=[VCF]                   (extension) Count on the GPU which base every record shows at the single-base sites of VCF (plain, gzip or bgzip) and write [sample].allele_counts.tsv (one GPU)\n"
+         "      --allele-mapq=[N]                 (extension) With --alleles: the least mapping quality of a counted record, 0..255. Default: 0 (not -q)\n"
+         "      --allele-baseq=[N]                (extension) With --alleles: the least base quality of a counted base, 0..93; lower ones count as low_baseq. Default: 0\n";
 }
 
 long to_long(const std::string &flag, const std::string &v) {
@@ -200,6 +206,9 @@ Options parse(int argc, char **argv) {
         else if (name == "gene-body") o.gene_body = true;
         else if (name == "tin") o.tin = true;
         else if (name == "cycles") o.cycles = true;
+        else if (name == "alleles") { o.alleles = need(); o.has_alleles = true; }
+        else if (name == "allele-mapq") { o.allele_mapq = to_long(name, need()); o.has_allele_mapq = true; }
+        else if (name == "allele-baseq") { o.allele_baseq = to_long(name, need()); o.has_allele_baseq = true; }
         else if (name == "mismatches") o.mismatches = true;
         else if (name == "mismatches-mapq") { o.mismatches_mapq = to_long(name, need()); o.has_mismatches_mapq = true; }
         else if (name == "coverage-mask") o.coverage_mask = to_ulong(name, need());
@@ -544,6 +553,7 @@ struct Session {
     // --mismatches: the header (contigs and lengths) the context's packed reference was made for; empty: none is kept
     bool mismatch_packed = false;
     std::vector<std::string> mismatch_contigs; std::vector<uint64_t> mismatch_lengths;
+    SiteFile sites;                                    // --alleles: the file's lines, parsed once; resolved against every input's header
     std::future<void> report_job;
     void finish_reports() { if (report_job.valid()) report_job.get(); }
 };
@@ -742,6 +752,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     // --gene-body, --tin: the model of this header's contigs and lengths (one for both), built when either changes
     if ((o.gene_body || o.tin) && (!S.gene_body_built || S.gene_body_lengths != in.lengths)) { S.gene_body.build(ann, in.lengths); S.gene_body_lengths = in.lengths; S.gene_body_built = true; }
     const int n_ref_bam = (int)bam_contigs.size();
+    // --alleles: the file's sites in this header's contig order
+    ResolvedSites sites;
+    if (o.has_alleles) resolve_sites(S.sites, bam_contigs, sites);
 
     // ---- the context and its inputs
     if (!S.gpu_asked) {
@@ -858,6 +871,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         // one input that the device decodes: the bases live on the device now (a cohort may meet another header, the host reader compares with them)
         if (!S.async_reports && (sam_input || device_decode)) { std::vector<std::vector<uint8_t>>().swap(S.fasta_seq); mismatch_seq.clear(); }
     }
+    // --alleles: the sites go to the device for this header; every decode window leaves the bases of its records at them there
+    if (o.has_alleles && (rc = rsqc_alleles_begin(gpu, n_ref_bam, (uint32_t)sites.tid.size(), sites.tid.data(), sites.pos.data(), (uint32_t)o.allele_mapq, (uint32_t)o.allele_baseq)) != RSQC_OK)
+        return gpu_failed(rc);
     S.t_loop0 = Clock::now();
     rc = RSQC_OK;
     // --sort: the loops below collect (no per-read kernel runs); rsqc_sort_end orders the records and runs them
@@ -946,6 +962,7 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         BamReader &bam = *in.reader;
         bam.set_cycles(o.cycles);
         if (o.mismatches) bam.set_mismatches(mismatch_seq, mismatch_len, (uint32_t)o.mismatches_mapq);
+        if (o.has_alleles) bam.set_alleles(sites.pos, sites.first, (uint32_t)o.allele_mapq, (uint32_t)o.allele_baseq);
         int cur = 0; bool in_flight = false;
         for (;;) {
             HostBatch &hb = S.bufs[cur];
@@ -978,6 +995,12 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
             bam.mismatches_sum(cyc, subst, byq, partial);
             rc = rsqc_mismatch_add(gpu, cyc.data(), subst.data(), byq.data(), &partial);
         }
+        if (o.has_alleles && rc == RSQC_OK) {
+            std::vector<uint64_t> counts;
+            rsqc_allele_info partial{};
+            bam.alleles_sum(counts, partial);
+            rc = rsqc_alleles_add(gpu, counts.empty() ? nullptr : counts.data(), &partial);
+        }
     }
     // (the stage ran at ingest: under --sort and --mark-duplicates the tables are those of the input)
     rsqc_cycle_info cycles{};
@@ -986,6 +1009,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
     rsqc_mismatch_info mismatches{};
     const uint64_t *mismatch_cyc = nullptr, *mismatch_subst = nullptr, *mismatch_byq = nullptr;
     if (o.mismatches && rc == RSQC_OK) rc = rsqc_mismatch_end(gpu, &mismatches, &mismatch_cyc, &mismatch_subst, &mismatch_byq);
+    rsqc_allele_info alleles{};
+    const uint64_t *allele_counts = nullptr;
+    if (o.has_alleles && rc == RSQC_OK) rc = rsqc_alleles_end(gpu, &alleles, &allele_counts);
     rsqc_sort_info sort_info{};
     if (o.sort && rc == RSQC_OK && (rc = rsqc_sort_end(gpu, &sort_info)) == RSQC_OK) {
         // the contigs in the order the SORTED records visit them: tid as unsigned, each once (the order of coverage.tsv)
@@ -1061,6 +1087,11 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
                  << ", no_seq " << mismatches.no_seq_records << ", inconsistent " << mismatches.inconsistent_records << ", compared " << mismatches.compared
                  << ", mismatched " << mismatches.mismatched << ", uncompared " << mismatches.uncompared << ", inserted " << mismatches.inserted << ", clipped " << mismatches.clipped
                  << ", deletions " << mismatches.deletions << ", beyond " << mismatches.beyond_bases << ", mismatch_ms " << mismatches.mismatch_ms << endl;
+        if (o.has_alleles)
+            cout << "Alleles: sites " << alleles.n_sites << ", skipped_lines " << S.sites.skipped_lines << ", off_header_lines " << sites.off_header_lines << ", duplicate_lines "
+                 << sites.duplicate_lines << ", records " << alleles.records << ", hit_records " << alleles.hit_records << ", observations " << alleles.observations << ", off_contig "
+                 << alleles.off_contig_records << ", low_mapq " << alleles.low_mapq_records << ", no_seq " << alleles.no_seq_records << ", inconsistent " << alleles.inconsistent_records
+                 << ", no_qual " << alleles.no_qual_records << ", alleles_ms " << alleles.alleles_ms << endl;
         cout << "Estimating library complexity..." << endl;
         cout << "Generating report" << endl;
     }
@@ -1096,6 +1127,9 @@ int run_sample(const Options &o, Annotation &ann, Session &S, Sample &sample, co
         if (!write_mismatch_cycles(stem + ".mismatch_cycles.tsv", mismatch_cyc)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".mismatch_cycles.tsv" << endl; return 8; }
         if (!write_mismatch_types(stem + ".mismatch_types.tsv", mismatch_subst)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".mismatch_types.tsv" << endl; return 8; }
         if (!write_mismatch_quality(stem + ".mismatch_quality.tsv", mismatch_byq)) { cerr << S.prefix << "Filesystem error:  cannot write " << stem << ".mismatch_quality.tsv" << endl; return 8; }
+    }
+    if (o.has_alleles && !write_allele_counts(out_dir + "/" + sample.name + ".allele_counts.tsv", bam_contigs, S.sites, sites, allele_counts)) {
+        cerr << S.prefix << "Filesystem error:  cannot write " << out_dir << "/" << sample.name << ".allele_counts.tsv" << endl; return 8;
     }
     if (!S.async_reports) {
         S.t_rep0 = Clock::now();
@@ -1442,6 +1476,15 @@ int main(int argc, char **argv) {
             if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
             if (many_gpus) throw ValidationError("--mismatches runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
         }
+        if ((o.has_allele_mapq || o.has_allele_baseq) && !o.has_alleles) throw ValidationError("--allele-mapq and --allele-baseq need --alleles");
+        if (o.has_allele_mapq && (o.allele_mapq < 0 || o.allele_mapq > 255)) throw ValidationError("--allele-mapq takes a mapping quality of 0..255");
+        if (o.has_allele_baseq && (o.allele_baseq < 0 || o.allele_baseq > 93)) throw ValidationError("--allele-baseq takes a base quality of 0..93");
+        if (o.has_alleles) {
+            // one table per context: the tables of shards would only need adding up, but that path is not built
+            bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
+            if (const char *e = getenv("RSQC_GPU_LIST")) many_gpus = many_gpus || strchr(e, ',') != nullptr;
+            if (many_gpus) throw ValidationError("--alleles runs on one GPU (it cannot be combined with --gpus, RSQC_GPUS or RSQC_GPU_LIST above one)");
+        }
         if (o.junctions) {
             // one table per context: the per-contig tables of shards would only need concatenating, but that path is not built
             bool many_gpus = o.gpus > 1 || (getenv("RSQC_GPUS") && atoi(getenv("RSQC_GPUS")) > 1);
@@ -1523,6 +1566,12 @@ int main(int argc, char **argv) {
         if (o.has_bed) {
             if (o.verbosity) cout << "Parsing BED intervals for fragment size computations..." << endl;
             ann.load_bed(o.bed);
+        }
+        if (o.has_alleles) {                                                  // parsed once; resolved against every input's header
+            std::string error;
+            const int bad = read_sites(o.alleles, S.sites, error);
+            if (bad == 10) { cerr << "Unable to open the sites: " << error << endl; return 10; }
+            if (bad) { cerr << "Failed to parse the sites: " << error << endl; return 11; }
         }
         S.base_chrom_id = ann.chrom_id; S.base_chrom_name = ann.chrom_name;
         if (!make_dirs(out_dir)) { cerr << "Filesystem error:  cannot create " << out_dir << endl; return 8; }

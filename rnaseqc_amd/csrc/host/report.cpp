@@ -622,4 +622,32 @@ bool write_mismatch_quality(const std::string &path, const uint64_t *byq) {
     return f.good();
 }
 
+// --alleles
+static int allele_base(char ch) { return ch == 'A' || ch == 'a' ? 0 : ch == 'C' || ch == 'c' ? 1 : ch == 'G' || ch == 'g' ? 2 : ch == 'T' || ch == 't' ? 3 : 4; }
+bool write_allele_counts(const std::string &path, const std::vector<std::string> &contigs, const SiteFile &file, const ResolvedSites &sites, const uint64_t *counts) {
+    std::ofstream f(path);
+    f << "contig\tposition\tid\tref\talt\tA\tC\tG\tT\tother\tdeleted\tlow_baseq\tref_count\talt_count" << NL;
+    for (size_t k = 0; k < sites.tid.size(); ++k) {
+        const SiteLine &s = file.lines[sites.line[k]];
+        const uint64_t *row = counts + k * RSQC_ALLELE_COLS;
+        f << contigs[(size_t)sites.tid[k]] << '\t' << (int64_t)sites.pos[k] + 1 << '\t' << s.id << '\t' << s.ref << '\t' << s.alt;
+        for (uint32_t c = 0; c < RSQC_ALLELE_COLS; ++c) f << '\t' << row[c];
+        const int r = allele_base(s.ref[0]);
+        bool taken[4] = {false, false, false, false};
+        uint64_t alt = 0;
+        for (size_t a = 0; a <= s.alt.size();) {                         // the entries of the comma list
+            size_t e = s.alt.find(',', a);
+            if (e == std::string::npos) e = s.alt.size();
+            if (e - a == 1) {
+                const int b = allele_base(s.alt[a]);
+                if (b < 4 && b != r && !taken[b]) { taken[b] = true; alt += row[b]; }
+            }
+            a = e + 1;
+        }
+        f << '\t' << row[r] << '\t' << alt << NL;
+    }
+    f.close();
+    return f.good();
+}
+
 }  // namespace rsqc_host

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gtf.hpp"
+#include "sites.hpp"
 
 namespace rsqc_host {
 
@@ -96,5 +97,11 @@ bool write_mismatch_cycles(const std::string &path, const uint64_t *cyc);
 bool write_mismatch_types(const std::string &path, const uint64_t *subst);
 // <output>/<sample>.mismatch_quality.tsv: quality, compared, mismatches, mismatch_rate; one row per quality 0..63 with compared > 0
 bool write_mismatch_quality(const std::string &path, const uint64_t *byq);
+
+// --alleles: the table of rsqc_alleles_end, counts[n_sites][7], with the sites it was counted for.
+// <output>/<sample>.allele_counts.tsv: contig, position (1-based), id, ref, alt, A, C, G, T, other, deleted, low_baseq, ref_count (the column of
+// REF) and alt_count (the sum of the columns of the distinct single-base A C G T entries of ALT's comma list that differ from REF; 0 when
+// there is none); one row per site in table order
+bool write_allele_counts(const std::string &path, const std::vector<std::string> &contigs, const SiteFile &file, const ResolvedSites &sites, const uint64_t *counts);
 
 }  // namespace rsqc_host

@@ -240,6 +240,23 @@ struct MismatchState {
     rsqc_mismatch_info info{};
 };
 
+// --alleles (rsqc_alleles_begin / rsqc_alleles_add / rsqc_alleles_end, rsqc_allele_api.cpp): the sites' positions and every contig's first
+// site on the device (uploaded at every begin), AL_S_WORDS scalar words and the cells [site][8] behind them in one buffer, the same in
+// page-locked memory (compacted to [site][7] behind rsqc_alleles_end), what the host added
+struct AlleleState {
+    bool active = false, done = false;
+    DevBuf pos, first, tab;
+    HostBuf h_tab;
+    int32_t n_contigs = 0;
+    uint32_t n_sites = 0, min_mapq = 0, min_baseq = 0;
+    bool merge = false;                                // RSQC_ALLELE_MERGE at rsqc_alleles_begin
+    uint64_t seen = 0;                                 // records of the pass's decode windows
+    std::vector<uint64_t> added;                       // rsqc_alleles_add: AL_S_WORDS + n_sites * 7 once there is something, summed on the host
+    uint64_t added_seen = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;   // around every window's kernel
+    rsqc_allele_info info{};
+};
+
 }  // namespace rsqc
 using namespace rsqc;            // (every unit that sees this header is host code of the library)
 
@@ -338,6 +355,7 @@ struct rsqc_ctx {
     TinState tin;
     CycleState cyc;
     MismatchState mm;
+    AlleleState al;
     MarkdupState markdup;
 
     // host results
@@ -397,6 +415,9 @@ void cycle_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forge
 // --mismatches: the window's kernel behind its parse stage (and behind --cycles'), on the main stream (rsqc_mismatch_api.cpp)
 int mismatch_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
 void mismatch_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the counts; free_buffers: the tables and the packed reference too
+// --alleles: the window's kernel behind --mismatches', on the main stream (rsqc_allele_api.cpp)
+int alleles_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
+void alleles_drop(rsqc_ctx *c, bool free_buffers);    // ends the mode and forgets the counts; free_buffers: the sites and the cells too
 // what the two have in common (rsqc_genemodel_api.cpp).  who: the public call, for the texts; what: the stage, as the texts name it.
 // A begin behind its own argument checks (the order of the calls, the model against the track's contigs; n_seg: its segments), the
 // figures its capacity texts end with, the model and the items reserved and copied (stream order: the caller synchronises); an end

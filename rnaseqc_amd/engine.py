@@ -100,6 +100,9 @@ def load_library():
         lib.rsqc_mismatch_begin.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_char_p), C.c_uint32]
         lib.rsqc_mismatch_add.argtypes = [vp, vp, vp, vp, C.POINTER(abi.MismatchInfo)]
         lib.rsqc_mismatch_end.argtypes = [vp, C.POINTER(abi.MismatchInfo), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        lib.rsqc_alleles_begin.argtypes = [vp, C.c_int32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32]
+        lib.rsqc_alleles_add.argtypes = [vp, vp, C.POINTER(abi.AlleleInfo)]
+        lib.rsqc_alleles_end.argtypes = [vp, C.POINTER(abi.AlleleInfo), C.POINTER(vp)]
         _lib = lib
     return _lib
 
@@ -117,6 +120,7 @@ EXPORTED_SYMBOLS = [
     "rsqc_tin_begin", "rsqc_tin_end", "rsqc_tin_rows",
     "rsqc_cycles_begin", "rsqc_cycles_add", "rsqc_cycles_end",
     "rsqc_mismatch_begin", "rsqc_mismatch_add", "rsqc_mismatch_end",
+    "rsqc_alleles_begin", "rsqc_alleles_add", "rsqc_alleles_end",
 ]
 
 
@@ -477,6 +481,32 @@ class Engine:
         self._check(self._l.rsqc_mismatch_end(self._h, C.byref(info), C.byref(p[0]), C.byref(p[1]), C.byref(p[2])))
         tabs = [abi._view(q.value, int(np.prod(shape)), np.uint64).copy().reshape(shape) for q, shape in zip(p, self._MM_SHAPES)]
         return ({f: getattr(info, f) for f, _ in abi.MismatchInfo._fields_}, *tabs)
+
+    # ---- base counts at known variant sites (rsqc_alleles_*) ---------------------------------------------------------------
+    def alleles_begin(self, n_contigs, tid, pos, min_mapq=0, min_baseq=0):
+        """Before the pass's first submit or decode_begin.  tid, pos: the sites, 0-based, strictly ascending by (tid, pos)."""
+        t, p = np.ascontiguousarray(tid, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int32)
+        assert t.ndim == 1 and t.shape == p.shape
+        self._check(self._l.rsqc_alleles_begin(self._h, int(n_contigs), int(t.size), abi.ptr(t), abi.ptr(p), int(min_mapq), int(min_baseq)))
+        self._allele_sites = int(t.size)
+
+    def alleles_add(self, counts, info: dict):
+        """Host-computed counts: counts [n_sites][7] (uint64, or None) and the fields of rsqc_allele_info."""
+        a = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        assert a is None or a.size == getattr(self, "_allele_sites", 0) * abi.ALLELE_COLS
+        part = abi.AlleleInfo()
+        for f, _ in abi.AlleleInfo._fields_:
+            setattr(part, f, info.get(f, 0))
+        self._check(self._l.rsqc_alleles_add(self._h, abi.ptr(a), C.byref(part)))
+
+    def alleles_end(self):
+        """Behind decode_end(): (the fields of rsqc_allele_info, counts [n_sites, 7]); the table is a copy."""
+        info = abi.AlleleInfo()
+        p = C.c_void_p()
+        self._check(self._l.rsqc_alleles_end(self._h, C.byref(info), C.byref(p)))
+        n = int(info.n_sites)
+        counts = abi._view(p.value, n * abi.ALLELE_COLS, np.uint64).copy().reshape(n, abi.ALLELE_COLS) if n else np.zeros((0, abi.ALLELE_COLS), np.uint64)
+        return {f: getattr(info, f) for f, _ in abi.AlleleInfo._fields_}, counts
 
     def read_device(self, ptr, count, dtype):
         """count items of dtype from a device pointer of this context (tests): hipMemcpy of the HIP runtime the library itself is
