@@ -85,6 +85,7 @@ struct BamReader::AlleleTab {
     std::thread::id thread;
 };
 
+BamReader::BamReader() = default;
 BamReader::~BamReader() {
     if (producer_started_) {
         { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
@@ -95,9 +96,6 @@ BamReader::~BamReader() {
     if (map_) munmap(const_cast<uint8_t *>(map_), map_size_);
     if (fp_) fclose(fp_);
     delete pool_;
-    for (CycleTab *t : cycle_tabs_) delete t;
-    for (MismatchTab *t : mismatch_tabs_) delete t;
-    for (AlleleTab *t : allele_tabs_) delete t;
     if (getenv("RSQC_HOST_PROFILE"))
         fprintf(stderr, "[bam] read %.3f  frame-blocks %.3f  inflate %.3f  move %.3f  frame-records %.3f  parse %.3f  merge %.3f s\n",
                 g_t_read, g_t_frame_blocks, g_t_inflate, g_t_move, g_t_frame_rec, g_t_parse, g_t_merge);
@@ -107,76 +105,46 @@ void BamReader::set_tags(const std::string &chimeric, const std::vector<std::str
     ch_tag_ = chimeric; filter_tags_ = filters;
 }
 
-BamReader::CycleTab *BamReader::cycle_tab_of_this_thread() {        // (once per chunk of 256 KB: the lock is not on a record's path)
-    const std::thread::id me = std::this_thread::get_id();
-    std::lock_guard<std::mutex> lk(cycle_mu_);
-    for (CycleTab *t : cycle_tabs_) if (t->thread == me) return t;
-    CycleTab *t = new CycleTab();
-    t->thread = me;
-    cycle_tabs_.push_back(t);
-    return t;
-}
 void BamReader::cycles_sum(std::vector<uint64_t> &base, std::vector<uint64_t> &qual, rsqc_cycle_info &info) {
     base.assign(rsqc::CYC_BASE_CELLS, 0); qual.assign(rsqc::CYC_QUAL_CELLS, 0);
     info = rsqc_cycle_info{};
-    std::lock_guard<std::mutex> lk(cycle_mu_);
-    for (const CycleTab *t : cycle_tabs_) {
-        for (size_t k = 0; k < base.size(); ++k) { base[k] += t->base[k]; info.bases += t->base[k]; }
-        for (size_t k = 0; k < qual.size(); ++k) qual[k] += t->qual[k];
-        const uint64_t *s = t->counts.s;
-        info.seen_records += t->seen; info.records += s[rsqc::CYC_S_RECORDS]; info.no_seq_records += s[rsqc::CYC_S_NO_SEQ];
+    cycle_tabs_.for_each([&](const CycleTab &t) {
+        for (size_t k = 0; k < base.size(); ++k) { base[k] += t.base[k]; info.bases += t.base[k]; }
+        for (size_t k = 0; k < qual.size(); ++k) qual[k] += t.qual[k];
+        const uint64_t *s = t.counts.s;
+        info.seen_records += t.seen; info.records += s[rsqc::CYC_S_RECORDS]; info.no_seq_records += s[rsqc::CYC_S_NO_SEQ];
         info.no_qual_records += s[rsqc::CYC_S_NO_QUAL]; info.beyond_bases += s[rsqc::CYC_S_BEYOND]; info.clamped_quals += s[rsqc::CYC_S_CLAMPED];
-    }
+    });
 }
 
-BamReader::MismatchTab *BamReader::mismatch_tab_of_this_thread() {
-    const std::thread::id me = std::this_thread::get_id();
-    std::lock_guard<std::mutex> lk(cycle_mu_);
-    for (MismatchTab *t : mismatch_tabs_) if (t->thread == me) return t;
-    MismatchTab *t = new MismatchTab();
-    t->thread = me;
-    mismatch_tabs_.push_back(t);
-    return t;
-}
 void BamReader::mismatches_sum(std::vector<uint64_t> &cyc, std::vector<uint64_t> &subst, std::vector<uint64_t> &byq, rsqc_mismatch_info &info) {
     cyc.assign(rsqc::MM_CYC_CELLS, 0); subst.assign(rsqc::MM_SUBST_CELLS, 0); byq.assign(rsqc::MM_BYQ_CELLS, 0);
     info = rsqc_mismatch_info{};
-    std::lock_guard<std::mutex> lk(cycle_mu_);
-    for (const MismatchTab *t : mismatch_tabs_) {
-        for (size_t k = 0; k < cyc.size(); ++k) cyc[k] += t->cyc[k];
-        for (size_t k = 0; k < subst.size(); ++k) subst[k] += t->subst[k];
-        for (size_t k = 0; k < byq.size(); ++k) byq[k] += t->byq[k];
-        const uint64_t *s = t->counts.s;
-        info.seen_records += t->seen; info.records += s[rsqc::MM_S_RECORDS]; info.no_reference_records += s[rsqc::MM_S_NO_REF]; info.low_mapq_records += s[rsqc::MM_S_LOW_MAPQ];
+    mismatch_tabs_.for_each([&](const MismatchTab &t) {
+        for (size_t k = 0; k < cyc.size(); ++k) cyc[k] += t.cyc[k];
+        for (size_t k = 0; k < subst.size(); ++k) subst[k] += t.subst[k];
+        for (size_t k = 0; k < byq.size(); ++k) byq[k] += t.byq[k];
+        const uint64_t *s = t.counts.s;
+        info.seen_records += t.seen; info.records += s[rsqc::MM_S_RECORDS]; info.no_reference_records += s[rsqc::MM_S_NO_REF]; info.low_mapq_records += s[rsqc::MM_S_LOW_MAPQ];
         info.no_seq_records += s[rsqc::MM_S_NO_SEQ]; info.inconsistent_records += s[rsqc::MM_S_INCONSISTENT]; info.no_qual_records += s[rsqc::MM_S_NO_QUAL];
         info.insertion_events += s[rsqc::MM_S_INS_EVENTS]; info.deletion_events += s[rsqc::MM_S_DEL_EVENTS]; info.deleted_bases += s[rsqc::MM_S_DEL_BASES];
         info.beyond_bases += s[rsqc::MM_S_BEYOND]; info.clamped_quals += s[rsqc::MM_S_CLAMPED];
-    }
+    });
     for (size_t k = 0; k < cyc.size(); ++k) {
         uint64_t *col[rsqc::MM_COLS] = {&info.compared, &info.mismatched, &info.uncompared, &info.inserted, &info.clipped, &info.deletions};
         *col[k % rsqc::MM_COLS] += cyc[k];
     }
 }
 
-BamReader::AlleleTab *BamReader::allele_tab_of_this_thread() {
-    const std::thread::id me = std::this_thread::get_id();
-    std::lock_guard<std::mutex> lk(cycle_mu_);
-    for (AlleleTab *t : allele_tabs_) if (t->thread == me) return t;
-    AlleleTab *t = new AlleleTab();
-    t->thread = me; t->counts.cells.counts = al_counts_.data();
-    allele_tabs_.push_back(t);
-    return t;
-}
 void BamReader::alleles_sum(std::vector<uint64_t> &counts, rsqc_allele_info &info) {
     info = rsqc_allele_info{};
-    std::lock_guard<std::mutex> lk(cycle_mu_);
     counts = al_counts_;
-    for (const AlleleTab *t : allele_tabs_) {
-        const uint64_t *s = t->counts.s;
-        info.seen_records += t->seen; info.records += s[rsqc::AL_S_RECORDS]; info.off_contig_records += s[rsqc::AL_S_OFF_CONTIG]; info.low_mapq_records += s[rsqc::AL_S_LOW_MAPQ];
+    allele_tabs_.for_each([&](const AlleleTab &t) {
+        const uint64_t *s = t.counts.s;
+        info.seen_records += t.seen; info.records += s[rsqc::AL_S_RECORDS]; info.off_contig_records += s[rsqc::AL_S_OFF_CONTIG]; info.low_mapq_records += s[rsqc::AL_S_LOW_MAPQ];
         info.no_seq_records += s[rsqc::AL_S_NO_SEQ]; info.inconsistent_records += s[rsqc::AL_S_INCONSISTENT]; info.no_qual_records += s[rsqc::AL_S_NO_QUAL];
         info.hit_records += s[rsqc::AL_S_HIT]; info.observations += s[rsqc::AL_S_OBS];
-    }
+    });
     info.n_sites = al_pos_.size();
 }
 
@@ -815,25 +783,28 @@ size_t BamReader::read_batch(HostBatch &out, size_t max_records) {
             memcpy(oqh2 + base + rec0[c], o.qh2.data(), m * sizeof(uint32_t));
             if (oumi) memcpy(oumi + base + rec0[c], o.umi.data(), m * sizeof(uint64_t));
             if (!o.cig.empty()) memcpy(ocig + cig_base + cig0[c], o.cig.data(), o.cig.size() * sizeof(uint32_t));
-            if (cycles_) {                                               // the chunk's records are final here: hop over them once more
-                CycleTab *t = cycle_tab_of_this_thread();
-                size_t q = o.start;
-                for (size_t k = 0; k < m; ++k) { const uint32_t bs = le32(bufp + q); (void)rsqc::cycle_count_bam(bufp + q, bs, t->counts); q += 4 + (size_t)bs; }
-                t->seen += m;
+            // the chunk's records are final here: hop over them once more, f(rec, block_size) for each
+            auto final_records = [&](auto f) {
+                const uint8_t *rec = bufp + o.start;
+                for (size_t k = 0; k < m; ++k) { const uint32_t bs = le32(rec); f(rec, bs); rec += 4 + (size_t)bs; }
+            };
+            if (cycles_) {
+                CycleTab &t = cycle_tabs_.of_this_thread();
+                final_records([&](const uint8_t *rec, uint32_t bs) { (void)rsqc::cycle_count_bam(rec, bs, t.counts); });
+                t.seen += m;
             }
             if (mismatches_) {
-                MismatchTab *t = mismatch_tab_of_this_thread();
+                MismatchTab &t = mismatch_tabs_.of_this_thread();
                 const rsqc::MismatchTextRef ref{mm_seq_.data(), mm_len_.data(), (int32_t)mm_seq_.size()};
-                size_t q = o.start;
-                for (size_t k = 0; k < m; ++k) { const uint32_t bs = le32(bufp + q); (void)rsqc::mismatch_count_bam(bufp + q, bs, ref, mm_min_mapq_, t->counts); q += 4 + (size_t)bs; }
-                t->seen += m;
+                final_records([&](const uint8_t *rec, uint32_t bs) { (void)rsqc::mismatch_count_bam(rec, bs, ref, mm_min_mapq_, t.counts); });
+                t.seen += m;
             }
             if (alleles_) {
-                AlleleTab *t = allele_tab_of_this_thread();
+                AlleleTab &t = allele_tabs_.of_this_thread();
+                t.counts.cells.counts = al_counts_.data();                   // (the table all workers share)
                 const rsqc::AlleleSites sites{al_pos_.data(), al_first_.data(), (int32_t)al_first_.size() - 1};
-                size_t q = o.start;
-                for (size_t k = 0; k < m; ++k) { const uint32_t bs = le32(bufp + q); (void)rsqc::allele_count_bam(bufp + q, bs, sites, al_min_mapq_, al_min_baseq_, t->counts); q += 4 + (size_t)bs; }
-                t->seen += m;
+                final_records([&](const uint8_t *rec, uint32_t bs) { (void)rsqc::allele_count_bam(rec, bs, sites, al_min_mapq_, al_min_baseq_, t.counts); });
+                t.seen += m;
             }
         });
         g_t_parse += now_s() - tp;

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <new>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -122,6 +123,28 @@ private:
     std::string error_;
 };
 
+// a table per worker thread, owned by whoever holds this: a worker takes its own once per chunk of 256 KB (the lock is not on a record's
+// path); whoever adds the tables up walks them under the same lock.  Tab has a member `std::thread::id thread`
+template <class Tab>
+class WorkerTabs {
+public:
+    Tab &of_this_thread() {
+        const std::thread::id me = std::this_thread::get_id();
+        std::lock_guard<std::mutex> lk(tabs_mu_);
+        for (auto &t : tabs_) if (t->thread == me) return *t;
+        tabs_.push_back(std::make_unique<Tab>());
+        tabs_.back()->thread = me;
+        return *tabs_.back();
+    }
+    template <class F> void for_each(F f) {
+        std::lock_guard<std::mutex> lk(tabs_mu_);
+        for (const auto &t : tabs_) f(*t);
+    }
+private:
+    std::mutex tabs_mu_;                                // guards tabs_ (the list, not the tables: each is written by its own thread only)
+    std::vector<std::unique_ptr<Tab>> tabs_;
+};
+
 class BamReader {
 public:
     bool open(const std::string &path);                 // false: cannot open / not a BAM
@@ -166,6 +189,7 @@ public:
     bool seek(uint64_t voff, uint64_t voff_end);
     int inflate_threads() const { return pool_inflate_ ? pool_inflate_->size() : 0; }
     int parse_threads() const { return pool_ ? pool_->size() : 0; }
+    BamReader();                         // (both in bam.cpp, where the workers' tables are complete types)
     ~BamReader();
 private:
     bool fill(size_t need);              // make at least `need` decompressed bytes available
@@ -208,20 +232,16 @@ private:
     uint64_t n_read_ = 0;
     bool cycles_ = false;
     struct CycleTab;                                    // one worker's tables
-    std::vector<CycleTab *> cycle_tabs_;                // (owned; a worker takes its own once, under cycle_mu_)
-    std::mutex cycle_mu_;
-    CycleTab *cycle_tab_of_this_thread();
+    WorkerTabs<CycleTab> cycle_tabs_;
     bool mismatches_ = false;
     std::vector<const char *> mm_seq_; std::vector<uint64_t> mm_len_; uint32_t mm_min_mapq_ = 0;
     struct MismatchTab;                                 // one worker's tables
-    std::vector<MismatchTab *> mismatch_tabs_;          // (owned; a worker takes its own once, under cycle_mu_)
-    MismatchTab *mismatch_tab_of_this_thread();
+    WorkerTabs<MismatchTab> mismatch_tabs_;
     bool alleles_ = false;
     std::vector<int32_t> al_pos_; std::vector<uint32_t> al_first_; uint32_t al_min_mapq_ = 0, al_min_baseq_ = 0;
     std::vector<uint64_t> al_counts_;                   // the shared table
     struct AlleleTab;                                   // one worker's scalar words
-    std::vector<AlleleTab *> allele_tabs_;              // (owned; a worker takes its own once, under cycle_mu_)
-    AlleleTab *allele_tab_of_this_thread();
+    WorkerTabs<AlleleTab> allele_tabs_;
     bool have_q_ = false; int32_t q_tid_ = 0, q_pos_ = 0;      // last primary mapped record seen (sort check across batches)
 };
 

@@ -19,17 +19,13 @@ template <bool MERGE> __global__ __launch_bounds__(AL_THREADS) void allele_sam_k
 // the record count is on the device: a grid for the most records the window can hold, a record per lane, at most 2048 workgroups (eight
 // per CU: a workgroup's end is at most nine LDS atomics per lane and sixteen global ones, so a large grid costs little and hides the
 // long records behind the short ones)
-static uint32_t allele_grid(uint32_t max_rec) {
-    const uint32_t need = (max_rec + AL_THREADS - 1) / AL_THREADS;
-    return need < 1u ? 1u : need > 2048u ? 2048u : need;
-}
 void launch_allele_bam(hipStream_t s, const DecodeWindow &W, const AlleleSites &sites, uint32_t min_mapq, uint32_t min_baseq, const AlleleTables &T, bool merge) {
-    const dim3 grid(allele_grid((W.end - W.start) / 36u + 1u));
+    const dim3 grid(capped_grid(decode_max_records(W), AL_THREADS, 2048u));
     if (merge) allele_bam_kernel<true><<<grid, AL_THREADS, 0, s>>>(MismatchBamSrc{W}, sites, min_mapq, min_baseq, T);
     else allele_bam_kernel<false><<<grid, AL_THREADS, 0, s>>>(MismatchBamSrc{W}, sites, min_mapq, min_baseq, T);
 }
 void launch_allele_sam(hipStream_t s, const SamWindow &S, const AlleleSites &sites, uint32_t min_mapq, uint32_t min_baseq, const AlleleTables &T, bool merge) {
-    const dim3 grid(allele_grid(S.rec_cap));
+    const dim3 grid(capped_grid(S.rec_cap, AL_THREADS, 2048u));
     if (merge) allele_sam_kernel<true><<<grid, AL_THREADS, 0, s>>>(MismatchSamSrc{S}, sites, min_mapq, min_baseq, T);
     else allele_sam_kernel<false><<<grid, AL_THREADS, 0, s>>>(MismatchSamSrc{S}, sites, min_mapq, min_baseq, T);
 }

@@ -1,11 +1,13 @@
 // rsqc_allele_api.cpp -- rsqc_alleles_begin / rsqc_alleles_add / rsqc_alleles_end: the sorted site list goes to the device at every begin
-// (a position per site, a first site per contig); every window of the device decode then leaves the bases its records show at those
-// sites in device-resident cells (one extra kernel per window, rsqc_allele.hip); at the end of the pass they are read back once, what
-// the host added is summed in, and the table is checked against the device's own count of its observations.
+// (a position per site, a first site per contig); the bases the records show at those sites (the kernel of rsqc_allele.hip behind every
+// window) in cells [site][8], compacted to [site][7] at the end and checked against the device's own count of its observations.  What
+// the stage shares with the other two behind a window is in rsqc_window_stage_api.cpp.
 #include "rsqc_ctx.h"
 #include "rsqc_allele.h"
 
 namespace {
+
+constexpr WindowNames NAMES{"rsqc_alleles_begin", "rsqc_alleles_add", "rsqc_alleles_end", "alleles"};
 
 size_t device_words(uint32_t n_sites) { return (size_t)AL_S_WORDS + (size_t)n_sites * AL_STRIDE; }
 size_t table_words(uint32_t n_sites) { return (size_t)AL_S_WORDS + (size_t)n_sites * AL_COLS; }
@@ -16,24 +18,16 @@ AlleleTables device_tables(const AlleleState &A) {
 }
 AlleleSites device_sites(const AlleleState &A) { return AlleleSites{(const int32_t *)A.pos.p, (const uint32_t *)A.first.p, A.n_contigs}; }
 
-int alleles_end_run(rsqc_ctx *c) {
+int alleles_finish(rsqc_ctx *c, double ms) {
     AlleleState &A = c->al;
     uint64_t *h = (uint64_t *)A.h_tab.p;
-    HIP_TRY(c, hipMemcpyAsync(h, A.tab.p, device_words(A.n_sites) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
     rsqc_allele_info &I = A.info;
     I = rsqc_allele_info{};
-    for (auto &pr : A.events) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) I.alleles_ms += ms;
-        c->event_pool.push_back(pr.first); c->event_pool.push_back(pr.second);
-    }
-    A.events.clear();
+    I.alleles_ms = ms;
     // [site][8] -> [site][7], in place and forwards (7 k + col <= 8 k + col)
     uint64_t *cells = h + AL_S_WORDS;
     for (size_t k = 1; k < A.n_sites; ++k) for (uint32_t col = 0; col < AL_COLS; ++col) cells[k * AL_COLS + col] = cells[k * AL_STRIDE + col];
-    if (!A.added.empty()) for (size_t k = 0; k < table_words(A.n_sites); ++k) h[k] += A.added[k];
+    window_sum_added(A, h, table_words(A.n_sites));
     const uint64_t *s = h;
     I.seen_records = A.seen + A.added_seen;
     I.records = s[AL_S_RECORDS]; I.off_contig_records = s[AL_S_OFF_CONTIG]; I.low_mapq_records = s[AL_S_LOW_MAPQ]; I.no_seq_records = s[AL_S_NO_SEQ];
@@ -54,38 +48,23 @@ namespace rsqc {
 
 void alleles_drop(rsqc_ctx *c, bool free_buffers) {
     AlleleState &A = c->al;
-    for (auto &pr : A.events) { c->event_pool.push_back(pr.first); c->event_pool.push_back(pr.second); }
-    A.events.clear();
-    A.active = A.done = false;
-    A.seen = A.added_seen = 0;
+    window_drop(c, A, free_buffers);
     A.n_sites = 0; A.n_contigs = 0;
-    A.added.clear(); A.added.shrink_to_fit();
-    A.info = rsqc_allele_info{};
-    if (free_buffers) { A.pos.release(); A.first.release(); A.tab.release(); A.h_tab.release(); }
+    if (free_buffers) { A.pos.release(); A.first.release(); }
 }
 
-// called by the decode for every window it enqueues, behind the window's parse stage
-int alleles_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S) {
-    AlleleState &A = c->al;
-    hipEvent_t e0 = get_event(c), e1 = get_event(c);
-    A.events.emplace_back(e0, e1);
-    HIP_TRY(c, hipEventRecord(e0, c->stream));
+void alleles_launch(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S) {
+    const AlleleState &A = c->al;
     if (S) launch_allele_sam(c->stream, *S, device_sites(A), A.min_mapq, A.min_baseq, device_tables(A), A.merge);
     else launch_allele_bam(c->stream, W, device_sites(A), A.min_mapq, A.min_baseq, device_tables(A), A.merge);
-    HIP_TRY(c, hipEventRecord(e1, c->stream));
-    return 0;
 }
 
 }  // namespace rsqc
 
 int rsqc_alleles_begin(rsqc_ctx *c, int32_t n_contigs, uint32_t n_sites, const int32_t *tid, const int32_t *pos, uint32_t min_mapq, uint32_t min_baseq) {
     if (!c) return RSQC_ERR_ARG;
-    if (c->sticky) return c->sticky;
-    if (c->finalized) return fail(c, RSQC_ERR_ARG, "rsqc_reset required after rsqc_finalize");
     AlleleState &A = c->al;
-    if (A.active) return fail(c, RSQC_ERR_ARG, "rsqc_alleles_begin: the context is counting alleles already");
-    if (c->dec.active || c->name_mode >= 0 || !c->batch_file_index.empty() || c->next_record_base)
-        return fail(c, RSQC_ERR_ARG, "rsqc_alleles_begin must precede the first submit and the rsqc_decode_begin of the pass");
+    if (int rc = window_begin_check(c, A, NAMES)) return rc;
     if (n_contigs < 0 || (n_sites > 0 && (!tid || !pos))) return fail(c, RSQC_ERR_ARG, "rsqc_alleles_begin: sites without tid or pos");
     if (min_mapq > 255u) return fail(c, RSQC_ERR_ARG, "rsqc_alleles_begin: min_mapq above 255");
     if (min_baseq > 93u) return fail(c, RSQC_ERR_ARG, "rsqc_alleles_begin: min_baseq above 93");
@@ -104,12 +83,11 @@ int rsqc_alleles_begin(rsqc_ctx *c, int32_t n_contigs, uint32_t n_sites, const i
     const size_t tab_bytes = device_words(n_sites) * 8;
     const std::string sizes = std::to_string((size_t)n_sites * 4) + " bytes for the positions, " + std::to_string(((size_t)n_contigs + 1) * 4) + " for the contigs, " +
                               std::to_string(tab_bytes) + " for the cells and as many in page-locked host memory";
-    if (!dev_reserve(A.pos, (size_t)std::max(n_sites, 1u) * 4) || !dev_reserve(A.first, ((size_t)n_contigs + 1) * 4) || !dev_reserve(A.tab, tab_bytes))
-        return fail(c, RSQC_ERR_CAPACITY, "rsqc_alleles_begin: no device memory for the sites (" + sizes + ")");
-    if (!host_reserve(A.h_tab, tab_bytes)) return fail(c, RSQC_ERR_CAPACITY, "rsqc_alleles_begin: no page-locked host memory for the table (" + sizes + ")");
+    const std::string no_device = "rsqc_alleles_begin: no device memory for the sites (" + sizes + ")";      // (the positions, the contigs and the cells under one text)
+    if (!dev_reserve(A.pos, (size_t)std::max(n_sites, 1u) * 4) || !dev_reserve(A.first, ((size_t)n_contigs + 1) * 4)) return fail(c, RSQC_ERR_CAPACITY, no_device);
+    if (int rc = window_tables(c, A, tab_bytes, no_device, "rsqc_alleles_begin: no page-locked host memory for the table (" + sizes + ")")) return rc;
     if (n_sites) HIP_TRY(c, hipMemcpyAsync(A.pos.p, pos, (size_t)n_sites * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(A.first.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(A.tab.p, 0, tab_bytes, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));                      // (the caller's arrays and `first` are read until here)
     A.n_contigs = n_contigs; A.n_sites = n_sites; A.min_mapq = min_mapq; A.min_baseq = min_baseq;
     const char *m = getenv("RSQC_ALLELE_MERGE");       // 0: an atomic per observation; 1: merged across the wave first (the table is the same)
@@ -120,17 +98,14 @@ int rsqc_alleles_begin(rsqc_ctx *c, int32_t n_contigs, uint32_t n_sites, const i
 
 int rsqc_alleles_add(rsqc_ctx *c, const uint64_t *counts, const rsqc_allele_info *partial) {
     if (!c || !partial) return RSQC_ERR_ARG;
-    if (c->sticky) return c->sticky;
     AlleleState &A = c->al;
-    if (!A.active) return fail(c, RSQC_ERR_ARG, "rsqc_alleles_begin must precede rsqc_alleles_add");
-    if (A.done) return fail(c, RSQC_ERR_ARG, "rsqc_alleles_add behind rsqc_alleles_end");
+    if (int rc = window_add_check(c, A, NAMES)) return rc;
     const size_t n_cells = (size_t)A.n_sites * AL_COLS;
     uint64_t sum = 0;
     if (counts) for (size_t k = 0; k < n_cells; ++k) sum += counts[k];
     if (sum != partial->observations)
         return fail(c, RSQC_ERR_ARG, "rsqc_alleles_add: counts add up to " + std::to_string(sum) + ", partial->observations is " + std::to_string(partial->observations));
-    if (A.added.empty()) A.added.assign(table_words(A.n_sites), 0);
-    uint64_t *s = A.added.data(), *a = s + AL_S_WORDS;
+    uint64_t *s = window_added(A, table_words(A.n_sites)), *a = s + AL_S_WORDS;
     if (counts) for (size_t k = 0; k < n_cells; ++k) a[k] += counts[k];
     s[AL_S_RECORDS] += partial->records; s[AL_S_OFF_CONTIG] += partial->off_contig_records; s[AL_S_LOW_MAPQ] += partial->low_mapq_records;
     s[AL_S_NO_SEQ] += partial->no_seq_records; s[AL_S_INCONSISTENT] += partial->inconsistent_records; s[AL_S_NO_QUAL] += partial->no_qual_records;
@@ -141,16 +116,8 @@ int rsqc_alleles_add(rsqc_ctx *c, const uint64_t *counts, const rsqc_allele_info
 
 int rsqc_alleles_end(rsqc_ctx *c, rsqc_allele_info *out, const uint64_t **counts) {
     if (!c || !out) return RSQC_ERR_ARG;
-    if (c->sticky) return c->sticky;
     AlleleState &A = c->al;
-    if (!A.active) return fail(c, RSQC_ERR_ARG, "rsqc_alleles_begin must precede rsqc_alleles_end");
-    if (c->dec.active) return fail(c, RSQC_ERR_ARG, "rsqc_decode_end must precede rsqc_alleles_end");
-    if (!A.done) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        const int rc = alleles_end_run(c);
-        if (rc) { (void)hipStreamSynchronize(c->stream); c->sticky = rc; return rc; }       // never a partial table: the pass is void until rsqc_reset
-        A.done = true;
-    }
+    if (int rc = window_end(c, A, NAMES, device_words(A.n_sites) * 8, alleles_finish)) return rc;
     *out = A.info;
     if (counts) *counts = (const uint64_t *)A.h_tab.p + AL_S_WORDS;
     return RSQC_OK;

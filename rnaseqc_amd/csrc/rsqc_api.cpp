@@ -136,9 +136,7 @@ void rsqc_destroy(rsqc_ctx *c) {
     track_drop(c, true);
     genebody_drop(c, true);
     tin_drop(c, true);
-    cycle_drop(c, true);
-    mismatch_drop(c, true);
-    alleles_drop(c, true);
+    window_stages_drop(c, true, true);
     for (auto &b : c->parked) b.release();
     free_sort_scratch(c->gc_scratch); free_sort_scratch(c->frag_scratch);
     c->d_ref_bits.release(); c->d_ref_off.release(); c->d_ref_len.release(); c->d_gc_bins.release(); c->d_exon_gc.release();
@@ -380,9 +378,7 @@ int rsqc_reset(rsqc_ctx *c) {
     track_drop(c, false);                              // (and so does the difference array)
     genebody_drop(c, false);
     tin_drop(c, false);
-    cycle_drop(c, false);                              // (the tables stay allocated)
-    mismatch_drop(c, false);                           // (and so do the tables and the packed reference)
-    alleles_drop(c, false);                            // (the buffers stay; the next begin uploads its own sites)
+    window_stages_drop(c, false, false);               // (the tables stay allocated, the packed reference and the sites' buffers too; the next begin uploads its own sites)
     const int rc = zero_accumulators(c);
     RSQC_TRACE("reset: enqueued");
     return rc;
@@ -405,9 +401,7 @@ int rsqc_clear_inputs(rsqc_ctx *c) {
     track_drop(c, false);
     genebody_drop(c, false);
     tin_drop(c, false);
-    cycle_drop(c, false);
-    mismatch_drop(c, true);                            // (the reference goes with the inputs)
-    alleles_drop(c, true);
+    window_stages_drop(c, false, true);                // (the reference and the sites go with the inputs, and those stages' tables with them)
     // an open decode stream is dropped with its carried-over bytes; its window buffers stay
     c->dec.active = false; c->dec.pending = false; c->dec.tail = 0;
     // the batches in flight hand their buffers back to the pools; what the pass has emitted so far goes with the arenas

@@ -210,50 +210,42 @@ struct TinState : GeneStage {
     HostBuf h_rows;                                    // every gene's row behind rsqc_tin_end
 };
 
-// --cycles (rsqc_cycles_begin / rsqc_cycles_add / rsqc_cycles_end, rsqc_cycle_api.cpp): the tables and their scalar words on the device
-// (CYC_TABLE_WORDS of 64 bits), the same in page-locked memory behind rsqc_cycles_end, what the host added
-struct CycleState {
+// What the stages behind every decode window hold alike (rsqc_window_stage_api.cpp): the tables and their scalar words on the device, the
+// same in page-locked memory behind the stage's end, what the host added, the events around every window's kernel
+struct WindowStage {
     bool active = false, done = false;
     DevBuf tab;
     HostBuf h_tab;
     uint64_t seen = 0;                                 // records of the pass's decode windows
-    std::vector<uint64_t> added;                       // rsqc_cycles_add: CYC_TABLE_WORDS once there is something, summed on the host
+    std::vector<uint64_t> added;                       // the stage's add: the words of the host's table once there is something, summed on the host
     uint64_t added_seen = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;   // around every window's kernel
+};
+
+// --cycles (rsqc_cycles_begin / rsqc_cycles_add / rsqc_cycles_end, rsqc_cycle_api.cpp): CYC_TABLE_WORDS of 64 bits
+struct CycleState : WindowStage {
     rsqc_cycle_info info{};
 };
 
 // --mismatches (rsqc_mismatch_begin / rsqc_mismatch_add / rsqc_mismatch_end, rsqc_mismatch_api.cpp): the reference at four bits per base
-// with a word offset and a length per contig -- kept across rsqc_reset, with the lengths it was packed for on the host --, the tables and
-// their scalar words on the device (MM_TABLE_WORDS of 64 bits), the same in page-locked memory behind rsqc_mismatch_end, what the host added
-struct MismatchState {
-    bool active = false, done = false, have_ref = false;
+// with a word offset and a length per contig -- kept across rsqc_reset, with the lengths it was packed for on the host --, and
+// MM_TABLE_WORDS of 64 bits
+struct MismatchState : WindowStage {
+    bool have_ref = false;
     DevBuf ref_words, ref_off, ref_len;
     std::vector<uint64_t> ref_length;                  // the n lengths of the packed reference
     uint32_t min_mapq = 0;
-    DevBuf tab;
-    HostBuf h_tab;
-    uint64_t seen = 0;                                 // records of the pass's decode windows
-    std::vector<uint64_t> added;                       // rsqc_mismatch_add: MM_TABLE_WORDS once there is something, summed on the host
-    uint64_t added_seen = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;   // around every window's kernel
     rsqc_mismatch_info info{};
 };
 
 // --alleles (rsqc_alleles_begin / rsqc_alleles_add / rsqc_alleles_end, rsqc_allele_api.cpp): the sites' positions and every contig's first
 // site on the device (uploaded at every begin), AL_S_WORDS scalar words and the cells [site][8] behind them in one buffer, the same in
-// page-locked memory (compacted to [site][7] behind rsqc_alleles_end), what the host added
-struct AlleleState {
-    bool active = false, done = false;
-    DevBuf pos, first, tab;
-    HostBuf h_tab;
+// page-locked memory (compacted to [site][7] behind rsqc_alleles_end); the host adds AL_S_WORDS + n_sites * 7 words
+struct AlleleState : WindowStage {
+    DevBuf pos, first;
     int32_t n_contigs = 0;
     uint32_t n_sites = 0, min_mapq = 0, min_baseq = 0;
     bool merge = false;                                // RSQC_ALLELE_MERGE at rsqc_alleles_begin
-    uint64_t seen = 0;                                 // records of the pass's decode windows
-    std::vector<uint64_t> added;                       // rsqc_alleles_add: AL_S_WORDS + n_sites * 7 once there is something, summed on the host
-    uint64_t added_seen = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;   // around every window's kernel
     rsqc_allele_info info{};
 };
 
@@ -409,15 +401,32 @@ void track_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forge
 void genebody_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the model and the sums
 // --tin: the stage behind rsqc_track_end (rsqc_tin_api.cpp)
 void tin_drop(rsqc_ctx *c, bool free_buffers);        // ends the mode and forgets the model and the rows
-// --cycles: the window's kernel behind its parse stage, on the main stream (rsqc_cycle_api.cpp; sam: W is pend_s.W)
-int cycle_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
-void cycle_drop(rsqc_ctx *c, bool free_buffers);      // ends the mode and forgets the counts
-// --mismatches: the window's kernel behind its parse stage (and behind --cycles'), on the main stream (rsqc_mismatch_api.cpp)
-int mismatch_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
-void mismatch_drop(rsqc_ctx *c, bool free_buffers);   // ends the mode and forgets the counts; free_buffers: the tables and the packed reference too
-// --alleles: the window's kernel behind --mismatches', on the main stream (rsqc_allele_api.cpp)
-int alleles_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
-void alleles_drop(rsqc_ctx *c, bool free_buffers);    // ends the mode and forgets the counts; free_buffers: the sites and the cells too
+// --cycles, --mismatches, --alleles (rsqc_cycle_api.cpp, rsqc_mismatch_api.cpp, rsqc_allele_api.cpp).  launch: the window's kernel on the main
+// stream (sam: W is pend_s.W); drop: ends the mode and forgets the counts; free_buffers: the tables too, and the packed reference / the sites
+void cycle_launch(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
+void cycle_drop(rsqc_ctx *c, bool free_buffers);
+void mismatch_launch(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
+void mismatch_drop(rsqc_ctx *c, bool free_buffers);
+void alleles_launch(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
+void alleles_drop(rsqc_ctx *c, bool free_buffers);
+// what the three have in common (rsqc_window_stage_api.cpp), and the one list of them, walked in the order of the kernels behind a
+// window: n_rec records submitted from a window; the stages' kernels behind its parse stage, each between a pair of events; every stage
+// dropped (free_inputs: the stages that were given a reference or sites at their begin free all they hold, whatever free_tables says)
+void window_stages_seen(rsqc_ctx *c, uint64_t n_rec);
+int window_stages_launch(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S);
+void window_stages_drop(rsqc_ctx *c, bool free_tables, bool free_inputs);
+// N: the stage's public calls and its noun, for the texts.  The order of the calls at a begin; the device and the page-locked table
+// reserved and the device one cleared, the caller's capacity texts; the common part of a drop; an add's guards, and the words the host
+// has added so far (sized at the first add); an end (the order of the calls, then once a pass: `bytes` read back, the events'
+// milliseconds handed to `finish`, which sums in what the host added -- window_sum_added -- fills the info and checks the table)
+struct WindowNames { const char *begin, *add, *end, *noun; };
+int window_begin_check(rsqc_ctx *c, const WindowStage &S, const WindowNames &N);
+int window_tables(rsqc_ctx *c, WindowStage &S, size_t bytes, const std::string &no_device, const std::string &no_host);
+void window_drop(rsqc_ctx *c, WindowStage &S, bool free_tables);
+int window_add_check(rsqc_ctx *c, const WindowStage &S, const WindowNames &N);
+uint64_t *window_added(WindowStage &S, size_t words);
+int window_end(rsqc_ctx *c, WindowStage &S, const WindowNames &N, size_t bytes, int (*finish)(rsqc_ctx *, double ms));
+void window_sum_added(const WindowStage &S, uint64_t *h, size_t words);
 // what the two have in common (rsqc_genemodel_api.cpp).  who: the public call, for the texts; what: the stage, as the texts name it.
 // A begin behind its own argument checks (the order of the calls, the model against the track's contigs; n_seg: its segments), the
 // figures its capacity texts end with, the model and the items reserved and copied (stream order: the caller synchronises); an end

@@ -19,16 +19,11 @@ __global__ __launch_bounds__(CYC_THREADS) void cycle_sam_kernel(CycleSamSrc src,
 // the record count is on the device: a grid for the most records the window can hold, at most 256 workgroups per tile -- with reads
 // shorter than a tile nearly all the work is the first tile's, and its workgroups (blockIdx.y == 0: dispatched first) then fill half the
 // chip's slots (256 CUs, two workgroups each) while the other tiles' pass through the rest; every wave takes 64 records per step
-static uint32_t cycle_grid_x(uint32_t max_rec) {
-    const uint32_t need = (max_rec + CYC_THREADS - 1) / CYC_THREADS;
-    return need < 1u ? 1u : need > 256u ? 256u : need;
-}
 void launch_cycle_bam(hipStream_t s, const DecodeWindow &W, const CycleTables &T) {
-    const uint32_t max_rec = (W.end - W.start) / 36u + 1u;
-    cycle_bam_kernel<<<dim3(cycle_grid_x(max_rec), CYC_TILES), CYC_THREADS, 0, s>>>(CycleBamSrc{W}, T);
+    cycle_bam_kernel<<<dim3(capped_grid(decode_max_records(W), CYC_THREADS, 256u), CYC_TILES), CYC_THREADS, 0, s>>>(CycleBamSrc{W}, T);
 }
 void launch_cycle_sam(hipStream_t s, const SamWindow &S, const CycleTables &T) {
-    cycle_sam_kernel<<<dim3(cycle_grid_x(S.rec_cap), CYC_TILES), CYC_THREADS, 0, s>>>(CycleSamSrc{S}, T);
+    cycle_sam_kernel<<<dim3(capped_grid(S.rec_cap, CYC_THREADS, 256u), CYC_TILES), CYC_THREADS, 0, s>>>(CycleSamSrc{S}, T);
 }
 
 }  // namespace rsqc

@@ -51,6 +51,14 @@ struct DecodeWindow {
     uint64_t *umi;                                         // the UMI keys (rsqc_batch.umi): null unless tags.umi_src selects a source
 };
 
+// The record count of a window is on the device when its kernels are launched: the most records its bytes can hold (at least 36 each),
+// and a grid of workgroups of `threads` over n such records, at least one and at most `cap` (each stage's launch says why its cap)
+inline uint32_t decode_max_records(const DecodeWindow &W) { return (W.end - W.start) / 36u + 1u; }
+inline uint32_t capped_grid(uint32_t n, uint32_t threads, uint32_t cap) {
+    const uint32_t need = (n + threads - 1) / threads;
+    return need < 1u ? 1u : need > cap ? cap : need;
+}
+
 RSQC_BAM_FN void decode_segment_bounds(const DecodeWindow &W, uint32_t s, uint32_t &lo, uint32_t &hi) {
     lo = W.start + s * DEC_SEG_BYTES;
     hi = (W.end - lo < DEC_SEG_BYTES) ? W.end : lo + DEC_SEG_BYTES;

@@ -254,7 +254,7 @@ void launch_decode_window(hipStream_t s, const DecodeWindow &W, uint32_t *scratc
     if (W.n_seg) bam_offsets_kernel<<<(W.n_seg + 255u) / 256u, 256, 0, s>>>(W);
     bam_parse_kernel<<<256 * 8, 256, 0, s>>>(W);
     // (the record count is on the device: grids for the most records the window's bytes can hold; surplus workgroups leave at once)
-    const uint32_t max_rec = (W.end - W.start) / 36u + 1u, list_blocks = (max_rec + DEC_LIST_BLOCK - 1) / DEC_LIST_BLOCK;
+    const uint32_t max_rec = decode_max_records(W), list_blocks = (max_rec + DEC_LIST_BLOCK - 1) / DEC_LIST_BLOCK;
     bam_lists_count_kernel<<<list_blocks, 256, 0, s>>>(W, lblk);
     bam_lists_top_kernel<<<1, 1024, 0, s>>>(W, lblk);
     bam_lists_write_kernel<<<list_blocks, 256, 0, s>>>(W, lblk);

@@ -144,9 +144,7 @@ int decode_finish(rsqc_ctx *c, rsqc_decode_window *out) {
         u->umi = W.umi;
         c->transient.push_back(u);
         D.next_file_index += S.n_rec; D.records += S.n_rec;
-        if (c->cyc.active) c->cyc.seen += S.n_rec;
-        if (c->mm.active) c->mm.seen += S.n_rec;
-        if (c->al.active) c->al.seen += S.n_rec;
+        window_stages_seen(c, S.n_rec);
         if ((rc = run_batch(c, u))) return rc;
     }
     if (left > D.head) {
@@ -270,9 +268,7 @@ int decode_enqueue(rsqc_ctx *c, const void *compressed, uint64_t compressed_byte
     } else
     launch_decode_window(c->stream, W, (uint32_t *)D.scratch.p);
     if (D.profile) HIP_TRY(c, hipEventRecord(D.pe[3], c->stream));
-    if (c->cyc.active && (rc = cycle_window(c, W, D.sam ? &D.pend_s : nullptr))) return rc;      // --cycles: SEQ / QUAL of the window's records
-    if (c->mm.active && (rc = mismatch_window(c, W, D.sam ? &D.pend_s : nullptr))) return rc;      // --mismatches: ... walked over the reference
-    if (c->al.active && (rc = alleles_window(c, W, D.sam ? &D.pend_s : nullptr))) return rc;        // --alleles: the bases at the sites
+    if ((rc = window_stages_launch(c, W, D.sam ? &D.pend_s : nullptr))) return rc;      // --cycles, --mismatches, --alleles: a kernel each over the window's records
     HIP_TRY(c, hipMemcpyAsync(D.h_sum, D.sum.p, sizeof(DecodeSummary), hipMemcpyDeviceToHost, c->stream));
     if (D.sam) HIP_TRY(c, hipMemcpyAsync(D.h_sam_st, D.sam_st.p, sizeof(SamStatus), hipMemcpyDeviceToHost, c->stream));
     D.pending = true; D.pend_limited = limited;

@@ -34,16 +34,11 @@ void launch_mismatch_pack(hipStream_t s, const uint8_t *ascii, uint64_t len, uin
 // the record count is on the device: a grid for the most records the window can hold, at most 256 workgroups (one per CU; the flush of a
 // workgroup is up to 6 000 global atomics, so more workgroups than the records can feed only add flushes); every wave takes 64 records
 // per step
-static uint32_t mismatch_grid(uint32_t max_rec) {
-    const uint32_t need = (max_rec + MM_THREADS - 1) / MM_THREADS;
-    return need < 1u ? 1u : need > 256u ? 256u : need;
-}
 void launch_mismatch_bam(hipStream_t s, const DecodeWindow &W, const MismatchPackedRef &ref, uint32_t min_mapq, const MismatchTables &T) {
-    const uint32_t max_rec = (W.end - W.start) / 36u + 1u;
-    mismatch_bam_kernel<<<dim3(mismatch_grid(max_rec)), MM_THREADS, 0, s>>>(MismatchBamSrc{W}, ref, min_mapq, T);
+    mismatch_bam_kernel<<<dim3(capped_grid(decode_max_records(W), MM_THREADS, 256u)), MM_THREADS, 0, s>>>(MismatchBamSrc{W}, ref, min_mapq, T);
 }
 void launch_mismatch_sam(hipStream_t s, const SamWindow &S, const MismatchPackedRef &ref, uint32_t min_mapq, const MismatchTables &T) {
-    mismatch_sam_kernel<<<dim3(mismatch_grid(S.rec_cap)), MM_THREADS, 0, s>>>(MismatchSamSrc{S}, ref, min_mapq, T);
+    mismatch_sam_kernel<<<dim3(capped_grid(S.rec_cap, MM_THREADS, 256u)), MM_THREADS, 0, s>>>(MismatchSamSrc{S}, ref, min_mapq, T);
 }
 
 }  // namespace rsqc

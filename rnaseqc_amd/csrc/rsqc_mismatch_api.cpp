@@ -1,13 +1,14 @@
 // rsqc_mismatch_api.cpp -- rsqc_mismatch_begin / rsqc_mismatch_add / rsqc_mismatch_end: the reference goes to the device once, four bits
-// per base; every window of the device decode then leaves the counts of its records' walk over SEQ, QUAL and that reference in
-// device-resident tables (one extra kernel per window, rsqc_mismatch.hip); at the end of the pass they are read back once, what the host
-// added is summed in, and the tables are checked against each other and against the device's own sum of lengths.
+// per base; the counts of the records' walk over SEQ, QUAL and that reference (the kernel of rsqc_mismatch.hip behind every window),
+// checked at the end against each other and against the device's own sum of lengths.  What the stage shares with the other two behind a
+// window is in rsqc_window_stage_api.cpp.
 #include "rsqc_ctx.h"
 #include "rsqc_mismatch.h"
 
 namespace {
 
 constexpr size_t TABLE_BYTES = (size_t)MM_TABLE_WORDS * 8;
+constexpr WindowNames NAMES{"rsqc_mismatch_begin", "rsqc_mismatch_add", "rsqc_mismatch_end", "mismatches"};
 constexpr size_t AT_SUBST = MM_CYC_CELLS, AT_BYQ = AT_SUBST + MM_SUBST_CELLS, AT_SCAL = AT_BYQ + MM_BYQ_CELLS;
 
 MismatchTables device_tables(const MismatchState &M) {
@@ -65,21 +66,13 @@ int pack_reference(rsqc_ctx *c, int32_t n, const uint64_t *length, const char *c
     return 0;
 }
 
-int mismatch_end_run(rsqc_ctx *c) {
+int mismatch_finish(rsqc_ctx *c, double ms) {
     MismatchState &M = c->mm;
     uint64_t *h = (uint64_t *)M.h_tab.p;
-    HIP_TRY(c, hipMemcpyAsync(h, M.tab.p, TABLE_BYTES, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
     rsqc_mismatch_info &I = M.info;
     I = rsqc_mismatch_info{};
-    for (auto &pr : M.events) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) I.mismatch_ms += ms;
-        c->event_pool.push_back(pr.first); c->event_pool.push_back(pr.second);
-    }
-    M.events.clear();
-    if (!M.added.empty()) for (size_t k = 0; k < MM_TABLE_WORDS; ++k) h[k] += M.added[k];
+    I.mismatch_ms = ms;
+    window_sum_added(M, h, MM_TABLE_WORDS);
     const uint64_t *cyc = h, *subst = h + AT_SUBST, *byq = h + AT_BYQ, *s = h + AT_SCAL;
     I.seen_records = M.seen + M.added_seen;
     I.records = s[MM_S_RECORDS]; I.no_reference_records = s[MM_S_NO_REF]; I.low_mapq_records = s[MM_S_LOW_MAPQ]; I.no_seq_records = s[MM_S_NO_SEQ];
@@ -117,38 +110,22 @@ int mismatch_end_run(rsqc_ctx *c) {
 namespace rsqc {
 
 void mismatch_drop(rsqc_ctx *c, bool free_buffers) {
-    MismatchState &M = c->mm;
-    for (auto &pr : M.events) { c->event_pool.push_back(pr.first); c->event_pool.push_back(pr.second); }
-    M.events.clear();
-    M.active = M.done = false;
-    M.seen = M.added_seen = 0;
-    M.added.clear();
-    M.info = rsqc_mismatch_info{};
-    if (free_buffers) { M.tab.release(); M.h_tab.release(); drop_reference(M); }
+    window_drop(c, c->mm, free_buffers);
+    if (free_buffers) drop_reference(c->mm);
 }
 
-// called by the decode for every window it enqueues, behind the window's parse stage
-int mismatch_window(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S) {
-    MismatchState &M = c->mm;
-    hipEvent_t e0 = get_event(c), e1 = get_event(c);
-    M.events.emplace_back(e0, e1);
-    HIP_TRY(c, hipEventRecord(e0, c->stream));
+void mismatch_launch(rsqc_ctx *c, const DecodeWindow &W, const SamWindow *S) {
+    const MismatchState &M = c->mm;
     if (S) launch_mismatch_sam(c->stream, *S, device_ref(M), M.min_mapq, device_tables(M));
     else launch_mismatch_bam(c->stream, W, device_ref(M), M.min_mapq, device_tables(M));
-    HIP_TRY(c, hipEventRecord(e1, c->stream));
-    return 0;
 }
 
 }  // namespace rsqc
 
 int rsqc_mismatch_begin(rsqc_ctx *c, int32_t n, const uint64_t *length, const char *const *sequence, uint32_t min_mapq) {
     if (!c) return RSQC_ERR_ARG;
-    if (c->sticky) return c->sticky;
-    if (c->finalized) return fail(c, RSQC_ERR_ARG, "rsqc_reset required after rsqc_finalize");
     MismatchState &M = c->mm;
-    if (M.active) return fail(c, RSQC_ERR_ARG, "rsqc_mismatch_begin: the context is counting mismatches already");
-    if (c->dec.active || c->name_mode >= 0 || !c->batch_file_index.empty() || c->next_record_base)
-        return fail(c, RSQC_ERR_ARG, "rsqc_mismatch_begin must precede the first submit and the rsqc_decode_begin of the pass");
+    if (int rc = window_begin_check(c, M, NAMES)) return rc;
     if (n < 0 || (n > 0 && !length)) return fail(c, RSQC_ERR_ARG, "rsqc_mismatch_begin: contigs without lengths");
     if (min_mapq > 255u) return fail(c, RSQC_ERR_ARG, "rsqc_mismatch_begin: min_mapq above 255");
     if (!sequence) {
@@ -160,9 +137,8 @@ int rsqc_mismatch_begin(rsqc_ctx *c, int32_t n, const uint64_t *length, const ch
     mismatch_drop(c, false);
     if (sequence) { if (int rc = pack_reference(c, n, length, sequence)) return rc; }
     const std::string sizes = std::to_string(TABLE_BYTES) + " bytes on the device and as many in page-locked host memory";
-    if (!dev_reserve(M.tab, TABLE_BYTES)) return fail(c, RSQC_ERR_CAPACITY, "rsqc_mismatch_begin: no device memory for the tables (" + sizes + ")");
-    if (!host_reserve(M.h_tab, TABLE_BYTES)) return fail(c, RSQC_ERR_CAPACITY, "rsqc_mismatch_begin: no page-locked host memory for the tables (" + sizes + ")");
-    HIP_TRY(c, hipMemsetAsync(M.tab.p, 0, TABLE_BYTES, c->stream));
+    if (int rc = window_tables(c, M, TABLE_BYTES, "rsqc_mismatch_begin: no device memory for the tables (" + sizes + ")",
+                               "rsqc_mismatch_begin: no page-locked host memory for the tables (" + sizes + ")")) return rc;
     M.min_mapq = min_mapq;
     M.active = true;
     return RSQC_OK;
@@ -170,17 +146,14 @@ int rsqc_mismatch_begin(rsqc_ctx *c, int32_t n, const uint64_t *length, const ch
 
 int rsqc_mismatch_add(rsqc_ctx *c, const uint64_t *cyc, const uint64_t *subst, const uint64_t *byq, const rsqc_mismatch_info *partial) {
     if (!c || !partial) return RSQC_ERR_ARG;
-    if (c->sticky) return c->sticky;
     MismatchState &M = c->mm;
-    if (!M.active) return fail(c, RSQC_ERR_ARG, "rsqc_mismatch_begin must precede rsqc_mismatch_add");
-    if (M.done) return fail(c, RSQC_ERR_ARG, "rsqc_mismatch_add behind rsqc_mismatch_end");
+    if (int rc = window_add_check(c, M, NAMES)) return rc;
     uint64_t col[MM_COLS] = {0, 0, 0, 0, 0, 0};
     if (cyc) for (size_t k = 0; k < MM_CYC_CELLS; ++k) col[k % MM_COLS] += cyc[k];
     if (col[MM_COMPARED] != partial->compared || col[MM_MISMATCH] != partial->mismatched || col[MM_UNCOMPARED] != partial->uncompared || col[MM_INSERTED] != partial->inserted ||
         col[MM_CLIPPED] != partial->clipped || col[MM_DELETIONS] != partial->deletions)
         return fail(c, RSQC_ERR_ARG, "rsqc_mismatch_add: compared .. deletions of partial are not the sums of the columns of cyc");
-    if (M.added.empty()) M.added.assign(MM_TABLE_WORDS, 0);
-    uint64_t *a = M.added.data(), *s = a + AT_SCAL;
+    uint64_t *a = window_added(M, MM_TABLE_WORDS), *s = a + AT_SCAL;
     if (cyc) for (size_t k = 0; k < MM_CYC_CELLS; ++k) a[k] += cyc[k];
     if (subst) for (size_t k = 0; k < MM_SUBST_CELLS; ++k) a[AT_SUBST + k] += subst[k];
     if (byq) for (size_t k = 0; k < MM_BYQ_CELLS; ++k) a[AT_BYQ + k] += byq[k];
@@ -195,16 +168,8 @@ int rsqc_mismatch_add(rsqc_ctx *c, const uint64_t *cyc, const uint64_t *subst, c
 
 int rsqc_mismatch_end(rsqc_ctx *c, rsqc_mismatch_info *out, const uint64_t **cyc, const uint64_t **subst, const uint64_t **byq) {
     if (!c || !out) return RSQC_ERR_ARG;
-    if (c->sticky) return c->sticky;
     MismatchState &M = c->mm;
-    if (!M.active) return fail(c, RSQC_ERR_ARG, "rsqc_mismatch_begin must precede rsqc_mismatch_end");
-    if (c->dec.active) return fail(c, RSQC_ERR_ARG, "rsqc_decode_end must precede rsqc_mismatch_end");
-    if (!M.done) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        const int rc = mismatch_end_run(c);
-        if (rc) { (void)hipStreamSynchronize(c->stream); c->sticky = rc; return rc; }       // never partial tables: the pass is void until rsqc_reset
-        M.done = true;
-    }
+    if (int rc = window_end(c, M, NAMES, TABLE_BYTES, mismatch_finish)) return rc;
     *out = M.info;
     const uint64_t *h = (const uint64_t *)M.h_tab.p;
     if (cyc) *cyc = h;

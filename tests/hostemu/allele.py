@@ -2,36 +2,17 @@
 by window into one table, the one-thread form over the same bytes, and the stand-alone sanitizer program over damaged records and site
 tables (allele_fuzz.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_SO = os.path.join(_HERE, "liballeleemu.so")
-_CSRC = os.path.join(_ROOT, "rnaseqc_amd", "csrc")
-_HEADERS = [os.path.join(_CSRC, h) for h in ("rsqc_allele.h", "rsqc_mismatch.h", "rsqc_cycle.h", "rsqc_bamrec.h", "rsqc_samrec.h", "rsqc_sam.h", "rsqc_decode.h", "rsqc_umi.h")] + \
-           [os.path.join(_ROOT, "include", "rnaseqc_amd.h"), os.path.join(_HERE, "wavemu.h")]
+from . import window_stage
+
 COLS, STRIDE, SCALARS = 7, 8, 16
 S_OFF_CONTIG, S_LOW_MAPQ, S_NO_SEQ, S_INCONSISTENT, S_RECORDS, S_NO_QUAL, S_HIT, S_OBS = range(1, 9)
 
 
-def _stale(out, srcs):
-    return not os.path.exists(out) or any(os.path.getmtime(out) < os.path.getmtime(s) for s in srcs)
-
-
-def build():
-    src = os.path.join(_HERE, "allele_emu.cpp")
-    if _stale(_SO, [src] + _HEADERS):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-unused-function", "-Wno-unused-variable", src, "-o", _SO])
-    return _SO
-
-
 def build_fuzz(exe):
-    """allele_fuzz.cpp as a program of its own under AddressSanitizer and UBSan (nothing is preloaded: it is run as a child process)."""
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", os.path.join(_HERE, "allele_fuzz.cpp"), "-o", exe])
-    return exe
+    return window_stage.build_fuzz("allele", exe)
 
 
 _lib = None
@@ -40,7 +21,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        _lib = C.CDLL(build())
+        _lib = C.CDLL(window_stage.build("allele", ("rsqc_allele.h", "rsqc_mismatch.h")))
         vp = C.c_void_p
         _lib.alemu_set_schedule_seed.argtypes = [C.c_ulonglong]
         _lib.alemu_set_merge.argtypes = [C.c_int]
@@ -101,16 +82,9 @@ class Table:
                     inconsistent_records=s[S_INCONSISTENT], no_qual_records=s[S_NO_QUAL], hit_records=s[S_HIT], observations=s[S_OBS], n_sites=_n_sites)
 
 
-def _run(call, windows, seed, *args):
+def _run(call, windows, seed):
     t, l = Table(STRIDE), lib()
-    l.alemu_set_schedule_seed(int(seed))
-    try:
-        for w in windows:
-            n = call(l, t, w, *args)
-            assert n >= 0
-            t.records += n
-    finally:
-        l.alemu_set_schedule_seed(0)
+    window_stage.run_windows(l.alemu_set_schedule_seed, seed, t, windows, lambda w: call(l, t, w))
     assert not t.cells[:, COLS:].any()                              # (the eighth cell of a line is never touched)
     return t
 

@@ -1,36 +1,17 @@
 """TEST HARNESS: the kernel body of --cycles (rnaseqc_amd/csrc/rsqc_cycle.h) on the 64-lane fiber emulation (see cycle_emu.cpp), window by
 window into one set of tables, and the stand-alone sanitizer program over damaged records (cycle_fuzz.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_SO = os.path.join(_HERE, "libcycleemu.so")
-_CSRC = os.path.join(_ROOT, "rnaseqc_amd", "csrc")
-_HEADERS = [os.path.join(_CSRC, h) for h in ("rsqc_cycle.h", "rsqc_bamrec.h", "rsqc_samrec.h", "rsqc_sam.h", "rsqc_decode.h", "rsqc_umi.h")] + \
-           [os.path.join(_ROOT, "include", "rnaseqc_amd.h"), os.path.join(_HERE, "wavemu.h")]
+from . import window_stage
+
 BASE_SHAPE, QUAL_SHAPE, SCALARS = (2, 512, 5), (2, 512, 64), 8
 S_RECORDS, S_NO_SEQ, S_NO_QUAL, S_BEYOND, S_CLAMPED, S_LEN_SUM = range(6)
 
 
-def _stale(out, srcs):
-    return not os.path.exists(out) or any(os.path.getmtime(out) < os.path.getmtime(s) for s in srcs)
-
-
-def build():
-    src = os.path.join(_HERE, "cycle_emu.cpp")
-    if _stale(_SO, [src] + _HEADERS):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-unused-function", "-Wno-unused-variable", src, "-o", _SO])
-    return _SO
-
-
 def build_fuzz(exe):
-    """cycle_fuzz.cpp as a program of its own under AddressSanitizer and UBSan (nothing is preloaded: it is run as a child process)."""
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", os.path.join(_HERE, "cycle_fuzz.cpp"), "-o", exe])
-    return exe
+    return window_stage.build_fuzz("cycle", exe)
 
 
 _lib = None
@@ -39,7 +20,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        _lib = C.CDLL(build())
+        _lib = C.CDLL(window_stage.build("cycle"))
         vp = C.c_void_p
         _lib.cycemu_set_schedule_seed.argtypes = [C.c_ulonglong]
         _lib.cycemu_bam.restype = C.c_longlong
@@ -68,29 +49,13 @@ class Tables:
 def run_bam(windows, front=0, n_blocks=1, seed=0):
     """windows: byte strings of complete BAM records; every one is a launch (four tiles x n_blocks workgroups) into the same tables."""
     t, l = Tables(), lib()
-    l.cycemu_set_schedule_seed(int(seed))
-    try:
-        for w in windows:
-            n = l.cycemu_bam(w, len(w), front, n_blocks, *t.ptrs())
-            assert n >= 0
-            t.records += n
-    finally:
-        l.cycemu_set_schedule_seed(0)
-    return t
+    return window_stage.run_windows(l.cycemu_set_schedule_seed, seed, t, windows, lambda w: l.cycemu_bam(w, len(w), front, n_blocks, *t.ptrs()))
 
 
 def run_sam(windows, front=0, n_blocks=1, seed=0):
     """windows: texts of complete lines; the first may start with header lines."""
     t, l = Tables(), lib()
-    l.cycemu_set_schedule_seed(int(seed))
-    try:
-        for w in windows:
-            n = l.cycemu_sam(w, len(w), front, 1 if t.records else 0, n_blocks, *t.ptrs())
-            assert n >= 0
-            t.records += n
-    finally:
-        l.cycemu_set_schedule_seed(0)
-    return t
+    return window_stage.run_windows(l.cycemu_set_schedule_seed, seed, t, windows, lambda w: l.cycemu_sam(w, len(w), front, 1 if t.records else 0, n_blocks, *t.ptrs()))
 
 
 def run_host_bam(stream):

@@ -15,6 +15,7 @@
 
 #include "../../rnaseqc_amd/csrc/rsqc_cycle.h"
 #include "../../rnaseqc_amd/csrc/rsqc_samrec.h"
+#include "stage_fuzz.h"
 
 using namespace rsqc;
 
@@ -31,38 +32,18 @@ struct Counts {
     }
 };
 
-uint64_t rng_state = 1;
-uint32_t rnd() { rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27; return (uint32_t)((rng_state * 0x2545F4914F6CDD1Dull) >> 33); }
-
-// a well-formed record without an aux tail: block_size ends with QUAL
-std::vector<uint8_t> make_record(uint32_t l_name, uint32_t n_cigar, uint32_t L, uint32_t flag) {
-    const uint32_t bs = 32u + l_name + 4u * n_cigar + (L + 1u) / 2u + L;
-    std::vector<uint8_t> r(4u + bs, 0);
-    auto put32 = [&](size_t at, uint32_t v) { memcpy(r.data() + at, &v, 4); };
-    put32(0, bs); put32(4, 0); put32(8, 100);
-    r[12] = (uint8_t)l_name; r[13] = 60;
-    const uint16_t nc = (uint16_t)n_cigar, fl = (uint16_t)flag;
-    memcpy(r.data() + 16, &nc, 2); memcpy(r.data() + 18, &fl, 2);
-    put32(20, L); put32(24, 0xFFFFFFFFu); put32(28, 0xFFFFFFFFu);
-    for (uint32_t k = 0; k + 1 < l_name; ++k) r[36 + k] = 'q';
-    for (uint32_t k = 0; k < n_cigar; ++k) put32(36u + l_name + 4u * k, (L << 4) | 0u);
-    uint8_t *seq = r.data() + 36u + l_name + 4u * n_cigar;
-    for (uint32_t k = 0; k < (L + 1u) / 2u; ++k) seq[k] = (uint8_t)(0x12u << (k & 1u) | 0x48u);
-    uint8_t *qual = seq + (L + 1u) / 2u;
-    for (uint32_t k = 0; k < L; ++k) qual[k] = (uint8_t)(k % 41u);
-    return r;
-}
+// (no tid or pos matters here: every operation is L M)
+std::vector<uint8_t> make_record(uint32_t l_name, uint32_t n_cigar, uint32_t L, uint32_t flag) { return ::make_record(l_name, std::vector<uint32_t>(n_cigar, op(L, 0)), L, flag, 0, 100); }
 
 // the record in a heap buffer of exactly `bytes` bytes; true: it counted something or the layout was accepted though it must not be
 bool counts_something(const std::vector<uint8_t> &rec, size_t bytes, bool must_refuse) {
-    uint8_t *heap = (uint8_t *)malloc(bytes ? bytes : 1);
-    memcpy(heap, rec.data(), bytes);
-    uint32_t bs; memcpy(&bs, heap, 4);
     Counts K;
-    uint32_t so, qo, L;
-    const bool laid = cycle_bam_layout(heap, bs, so, qo, L);
-    const bool counted = cycle_count_bam(heap, bs, K.c);
-    free(heap);
+    bool laid = false, counted = false;
+    on_exact_heap(rec, bytes, [&](const uint8_t *heap, uint32_t bs) {
+        uint32_t so, qo, L;
+        laid = cycle_bam_layout(heap, bs, so, qo, L);
+        counted = cycle_count_bam(heap, bs, K.c);
+    });
     return must_refuse && (laid || counted || !K.empty());
 }
 
@@ -72,7 +53,7 @@ int fail(const char *what, long long a, long long b) { printf("cycle_fuzz: COUNT
 
 int main(int argc, char **argv) {
     const long n_random = argc > 1 ? atol(argv[1]) : 20000;
-    rng_state = argc > 2 ? (uint64_t)atoll(argv[2]) * 0x9E3779B97F4A7C15ull | 1ull : 1ull;
+    seed_rnd(argc, argv);
     long long cases = 0;
     // a sound record counts (the harness would otherwise pass for the wrong reason)
     {
@@ -150,15 +131,9 @@ int main(int argc, char **argv) {
         std::vector<uint8_t> r = make_record(1u + rnd() % 12u, rnd() % 4u, rnd() % 300u, rnd() & 0xFFFu);
         const uint32_t hits = 1u + rnd() % 3u;
         for (uint32_t h = 0; h < hits; ++h) r[rnd() % 36u] = (uint8_t)rnd();
-        uint32_t bs; memcpy(&bs, r.data(), 4);
-        if (bs > r.size() - 4u) { bs = (uint32_t)(rnd() % (r.size() - 3u)); memcpy(r.data(), &bs, 4); }      // (the framing never hands on a record that leaves its window)
-        const size_t bytes = 4u + (size_t)bs < 36u ? 36u : 4u + (size_t)bs;
-        r.resize(bytes > r.size() ? bytes : r.size());
-        uint8_t *heap = (uint8_t *)malloc(bytes);
-        memcpy(heap, r.data(), bytes);
+        const size_t bytes = clamp_block_size(r);
         Counts K;
-        if (!cycle_count_bam(heap, bs, K.c)) ++refused;
-        free(heap);
+        on_exact_heap(r, bytes, [&](const uint8_t *heap, uint32_t bs) { if (!cycle_count_bam(heap, bs, K.c)) ++refused; });
     }
     printf("cycle_fuzz: %lld cases, %lld of %ld random ones refused\n", cases, refused, n_random);
     return 0;

@@ -2,36 +2,17 @@
 window by window into one set of tables, the one-thread form over the same bytes, and the stand-alone sanitizer program over damaged
 records (mismatch_fuzz.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_SO = os.path.join(_HERE, "libmismatchemu.so")
-_CSRC = os.path.join(_ROOT, "rnaseqc_amd", "csrc")
-_HEADERS = [os.path.join(_CSRC, h) for h in ("rsqc_mismatch.h", "rsqc_cycle.h", "rsqc_bamrec.h", "rsqc_samrec.h", "rsqc_sam.h", "rsqc_decode.h", "rsqc_umi.h")] + \
-           [os.path.join(_ROOT, "include", "rnaseqc_amd.h"), os.path.join(_HERE, "wavemu.h")]
+from . import window_stage
+
 CYC_SHAPE, SUBST_SHAPE, BYQ_SHAPE, SCALARS = (2, 512, 6), (2, 4, 4), (64, 2), 16
 S_NO_REF, S_LOW_MAPQ, S_NO_SEQ, S_INCONSISTENT, S_RECORDS, S_NO_QUAL, S_BEYOND, S_CLAMPED, S_INS_EVENTS, S_DEL_EVENTS, S_DEL_BASES, S_LEN_SUM = range(1, 13)
 
 
-def _stale(out, srcs):
-    return not os.path.exists(out) or any(os.path.getmtime(out) < os.path.getmtime(s) for s in srcs)
-
-
-def build():
-    src = os.path.join(_HERE, "mismatch_emu.cpp")
-    if _stale(_SO, [src] + _HEADERS):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-unused-function", "-Wno-unused-variable", src, "-o", _SO])
-    return _SO
-
-
 def build_fuzz(exe):
-    """mismatch_fuzz.cpp as a program of its own under AddressSanitizer and UBSan (nothing is preloaded: it is run as a child process)."""
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", os.path.join(_HERE, "mismatch_fuzz.cpp"), "-o", exe])
-    return exe
+    return window_stage.build_fuzz("mismatch", exe)
 
 
 _lib = None
@@ -40,7 +21,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        _lib = C.CDLL(build())
+        _lib = C.CDLL(window_stage.build("mismatch", ("rsqc_mismatch.h",)))
         vp = C.c_void_p
         tabs = [vp, vp, vp, vp]
         _lib.mmemu_set_schedule_seed.argtypes = [C.c_ulonglong]
@@ -96,29 +77,13 @@ class Tables:
 def run_bam(windows, min_mapq=0, front=0, n_blocks=1, seed=0):
     """windows: byte strings of complete BAM records; every one is a launch of n_blocks workgroups into the same tables."""
     t, l = Tables(), lib()
-    l.mmemu_set_schedule_seed(int(seed))
-    try:
-        for w in windows:
-            n = l.mmemu_bam(w, len(w), front, n_blocks, min_mapq, *t.ptrs())
-            assert n >= 0
-            t.records += n
-    finally:
-        l.mmemu_set_schedule_seed(0)
-    return t
+    return window_stage.run_windows(l.mmemu_set_schedule_seed, seed, t, windows, lambda w: l.mmemu_bam(w, len(w), front, n_blocks, min_mapq, *t.ptrs()))
 
 
 def run_sam(windows, min_mapq=0, front=0, n_blocks=1, seed=0):
     """windows: texts of complete lines; the first may start with header lines."""
     t, l = Tables(), lib()
-    l.mmemu_set_schedule_seed(int(seed))
-    try:
-        for w in windows:
-            n = l.mmemu_sam(w, len(w), front, 1 if t.records else 0, n_blocks, min_mapq, *t.ptrs())
-            assert n >= 0
-            t.records += n
-    finally:
-        l.mmemu_set_schedule_seed(0)
-    return t
+    return window_stage.run_windows(l.mmemu_set_schedule_seed, seed, t, windows, lambda w: l.mmemu_sam(w, len(w), front, 1 if t.records else 0, n_blocks, min_mapq, *t.ptrs()))
 
 
 def run_host(stream, min_mapq=0, sam=False):

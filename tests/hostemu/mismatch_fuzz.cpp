@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../rnaseqc_amd/csrc/rsqc_mismatch.h"
+#include "stage_fuzz.h"
 
 using namespace rsqc;
 
@@ -43,29 +44,6 @@ struct Counts {
     }
 };
 
-uint64_t rng_state = 1;
-uint32_t rnd() { rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27; return (uint32_t)((rng_state * 0x2545F4914F6CDD1Dull) >> 33); }
-
-// a well-formed record without an aux tail: block_size ends with QUAL
-std::vector<uint8_t> make_record(uint32_t l_name, const std::vector<uint32_t> &ops, uint32_t L, uint32_t flag, int32_t tid, int32_t pos) {
-    const uint32_t n_cigar = (uint32_t)ops.size(), bs = 32u + l_name + 4u * n_cigar + (L + 1u) / 2u + L;
-    std::vector<uint8_t> r(4u + bs, 0);
-    auto put32 = [&](size_t at, uint32_t v) { memcpy(r.data() + at, &v, 4); };
-    put32(0, bs); put32(4, (uint32_t)tid); put32(8, (uint32_t)pos);
-    r[12] = (uint8_t)l_name; r[13] = 60;
-    const uint16_t nc = (uint16_t)n_cigar, fl = (uint16_t)flag;
-    memcpy(r.data() + 16, &nc, 2); memcpy(r.data() + 18, &fl, 2);
-    put32(20, L); put32(24, 0xFFFFFFFFu); put32(28, 0xFFFFFFFFu);
-    for (uint32_t k = 0; k + 1 < l_name; ++k) r[36 + k] = 'q';
-    for (uint32_t k = 0; k < n_cigar; ++k) put32(36u + l_name + 4u * k, ops[k]);
-    uint8_t *seq = r.data() + 36u + l_name + 4u * n_cigar;
-    for (uint32_t k = 0; k < (L + 1u) / 2u; ++k) seq[k] = (uint8_t)(0x12u << (k & 1u) | 0x48u);
-    uint8_t *qual = seq + (L + 1u) / 2u;
-    for (uint32_t k = 0; k < L; ++k) qual[k] = (uint8_t)(k % 41u);
-    return r;
-}
-uint32_t op(uint32_t n, uint32_t code) { return n << 4 | code; }
-
 struct Reference {
     char *bases;                                       // exactly REF_LEN bytes on the heap
     const char *seq[2]; uint64_t len[2];
@@ -80,11 +58,8 @@ struct Reference {
 
 // the record in a heap buffer of exactly `bytes` bytes, counted into K; what mismatch_count_bam answered
 bool count(const std::vector<uint8_t> &rec, size_t bytes, const Reference &R, Counts &K) {
-    uint8_t *heap = (uint8_t *)malloc(bytes ? bytes : 1);
-    memcpy(heap, rec.data(), bytes);
-    uint32_t bs; memcpy(&bs, heap, 4);
-    const bool counted = mismatch_count_bam(heap, bs, R.ref(), 0, K.c);
-    free(heap);
+    bool counted = false;
+    on_exact_heap(rec, bytes, [&](const uint8_t *heap, uint32_t bs) { counted = mismatch_count_bam(heap, bs, R.ref(), 0, K.c); });
     return counted;
 }
 bool counts_something(const std::vector<uint8_t> &rec, size_t bytes, const Reference &R) {
@@ -98,7 +73,7 @@ int fail(const char *what, long long a, long long b) { printf("mismatch_fuzz: WR
 
 int main(int argc, char **argv) {
     const long n_random = argc > 1 ? atol(argv[1]) : 20000;
-    rng_state = argc > 2 ? (uint64_t)atoll(argv[2]) * 0x9E3779B97F4A7C15ull | 1ull : 1ull;
+    seed_rnd(argc, argv);
     const Reference R;
     long long cases = 0;
     // a sound record counts (the harness would otherwise pass for the wrong reason)
@@ -181,10 +156,7 @@ int main(int argc, char **argv) {
         std::vector<uint8_t> r = make_record(1u + rnd() % 12u, ops, L, rnd() & 0xFFFu, (int32_t)(rnd() % 3u), (int32_t)(rnd() % 1100u) - 50);
         const uint32_t hits = rnd() % 4u;
         for (uint32_t h = 0; h < hits; ++h) r[rnd() % (36u + (rnd() & 1u ? 24u : 0u)) % r.size()] = (uint8_t)rnd();
-        uint32_t bs; memcpy(&bs, r.data(), 4);
-        if (bs > r.size() - 4u) { bs = (uint32_t)(rnd() % (r.size() - 3u)); memcpy(r.data(), &bs, 4); }      // (the framing never hands on a record that leaves its window)
-        const size_t bytes = 4u + (size_t)bs < 36u ? 36u : 4u + (size_t)bs;
-        r.resize(bytes > r.size() ? bytes : r.size());
+        const size_t bytes = clamp_block_size(r);
         Counts K;
         if (!count(r, bytes, R, K)) ++refused;
     }
